@@ -8,6 +8,14 @@ scaling; the corpus bytes do not depend on N). One "step" = one evaluation of ev
 the rank's shard with the batch resident in HBM.
 
   python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c4|c5] [--resources TOTAL]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the corpus (or reads the copy build() left in
+build/corpus), flattens it, warms up, times the K steps and prints the result line. --dump-outputs DIR then writes
+what the last timed step computed (verdict totals and a seeded sample of the verdict matrix) as DIR/<name>.npy.
+--full adds every other leg, each outside the timed region: the byte-accounting evaluation and the serialised
+phase times (the roofline block), the report-assembly gathers, the end-to-end leg and the CPU baseline with its
+parity checks; the --no-* options drop single legs of a --full run.
 
 --gpus N > 1 without an external launcher: this script starts N rank processes itself (before any GPU call) and
 exits with the worst rank's code; under torch.distributed.run it is one rank. Every rank evaluates its own shard
@@ -28,6 +36,9 @@ METRIC = "resource×rule evals/sec (background scan, PSS+best-practices) at 1/2/
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s measured streaming copy
 SEED = 0x4B59564E
 CPU_STATUSES = ("fallback", "panic", "nondeterministic")  # pairs the device hands to the CPU engine
+CORPUS_CACHE = os.path.join(ROOT, "build", "corpus")  # build() leaves the default workload's corpus here
+DUMP_SAMPLE_BYTES = 48 << 20  # --dump-outputs: cap on the sampled verdict matrix (float32)
+DUMP_BLOCK = 4096  # resources per sampled block
 
 
 def log(*a):
@@ -515,6 +526,42 @@ def shard(total, rank, world, chunk=20000):
     return cut(rank), cut(rank + 1)
 
 
+def dump_sample_blocks(n, nrules):
+    """--dump-outputs: the input-order resource ranges [res0, res0 + len) whose verdicts are written: every resource
+    while the float32 matrix fits DUMP_SAMPLE_BYTES, else a seeded choice of DUMP_BLOCK-resource blocks (the same
+    ones in every run with the same arguments)"""
+    import numpy as np
+    cols = max(1, DUMP_SAMPLE_BYTES // (4 * max(1, nrules)))
+    if n <= cols:
+        return [(0, n)]
+    blk = min(DUMP_BLOCK, cols)
+    nblocks = (n + blk - 1) // blk
+    pick = np.sort(np.random.default_rng(SEED).choice(nblocks, size=min(nblocks, cols // blk), replace=False))
+    return [(int(b) * blk, min(blk, n - int(b) * blk)) for b in pick]
+
+
+def dump_outputs(out_dir, batch, res, device, rank, world):
+    """--dump-outputs DIR: what the last timed evaluation handed its caller, as DIR/<name>.npy (<name>.rank<r>.npy on
+    ranks of a multi-GPU run): `counts` float64 [8] and `rule_counts` float64 [rules, 8], the verdict totals by
+    KYV_ST_* status; `verdicts` float32 [rules, sampled resources], the verdicts the evaluation left resident on the
+    device (Batch.resident_status), and `verdict_resources` float64 [sampled resources], their input-order indices."""
+    import numpy as np
+    from kyverno_amd import _lib as K
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else ".rank%d" % rank
+    nrules = len(batch.ruleset.rules)
+    blocks = dump_sample_blocks(batch.n, nrules)
+    st = np.concatenate([batch.resident_status(device=device, res0=r0, nres=k) for r0, k in blocks], axis=1)
+    idx = np.concatenate([np.arange(r0, r0 + k, dtype=np.float64) for r0, k in blocks])
+    arrays = {"counts": np.array([res.counts[s] for s in K.STATUS_NAMES], dtype=np.float64),
+              "rule_counts": res.rule_counts.astype(np.float64),
+              "verdicts": (st & 7).astype(np.float32),
+              "verdict_resources": idx}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -523,15 +570,30 @@ def main():
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c4", "c5"])
     ap.add_argument("--resources", type=int, default=0,
                     help="total resources over all GPUs (default 10M c3, 1M c2 / c4 / c5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (flatten + H2D + eval + D2H) leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg outside the headline figure: byte accounting and serialised phase times "
+                         "(roofline), report gathers, end to end, CPU baseline and parity (the --no-* options drop one)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity leg")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full: skip the end-to-end (flatten + H2D + eval + D2H) leg")
     ap.add_argument("--no-account", action="store_true",
-                    help="profiling runs: skip the byte-accounting evaluation (its kernels share the product's names)")
-    ap.add_argument("--no-serial", action="store_true", help="profiling runs: skip the serialised phase-time evaluations")
+                    help="--full profiling runs: skip the byte-accounting evaluation (its kernels share the product's "
+                         "names)")
+    ap.add_argument("--no-serial", action="store_true",
+                    help="--full profiling runs: skip the serialised phase-time evaluations")
     ap.add_argument("--gather", action="store_true",
-                    help="time the RCCL all-gather of the resident results (loads torch first: KYV_TORCH_FIRST)")
-    ap.add_argument("--no-gather", action="store_true", help="skip the report-assembly gather after the timed region")
+                    help="--full: time the RCCL all-gather of the resident results through torch.distributed (loads "
+                         "torch first: KYV_TORCH_FIRST)")
+    ap.add_argument("--no-gather", action="store_true",
+                    help="--full: skip the report-assembly gather after the timed region")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step's results: --steps must be at least 1")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_e2e = args.no_account = args.no_serial = args.no_gather = True
+        args.gather = False
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
 
@@ -547,9 +609,13 @@ def main():
     policies = load_policies(args.workload)
 
     t0 = time.time()
-    data, nsl = synth.cached_corpus(hi - lo, kind=kind, seed=SEED, start=lo)
+    # the corpus build() left in the tree (the default workload's, one GPU) is read instead of generated: the same bytes
+    prebuilt = not os.environ.get("KYV_CORPUS_CACHE") and \
+        synth.corpus_is_cached(CORPUS_CACHE, hi - lo, kind=kind, seed=SEED, start=lo)
+    data, nsl = synth.cached_corpus(hi - lo, kind=kind, seed=SEED, start=lo, cache_dir=CORPUS_CACHE if prebuilt else None)
     t_gen = time.time() - t0
-    log("rank %d: generated resources [%d, %d) of %d (%.1f MB) in %.1f s" % (rank, lo, hi, total, len(data) / 1e6, t_gen))
+    log("rank %d: %s resources [%d, %d) of %d (%.1f MB) in %.1f s" % (
+        rank, "read the prebuilt corpus," if prebuilt else "generated", lo, hi, total, len(data) / 1e6, t_gen))
     t0 = time.time()
     rs = E.Ruleset(policies)
     t_compile = time.time() - t0
@@ -587,8 +653,8 @@ def main():
         bytes_per_eval = acct.alg_bytes / max(1, pairs)
         acct_counts_ok = acct.counts == counts  # the accounting build decides every pair as the product build does
         del acct
-    log("rank %d: %.1f algorithmic bytes per eval (device-counted over the shard, %.1f s): %s" % (
-        rank, bytes_per_eval, time.time() - t0, phase_bytes))
+        log("rank %d: %.1f algorithmic bytes per eval (device-counted over the shard, %.1f s): %s" % (
+            rank, bytes_per_eval, time.time() - t0, phase_bytes))
 
     barrier(pg)
     t0 = time.perf_counter()
@@ -602,6 +668,10 @@ def main():
     barrier(pg)
     dt = time.perf_counter() - t0
     dt_max = all_max(pg, dt)
+    dumped = None
+    if args.dump_outputs:  # before any later evaluation replaces the last timed step's resident results
+        dumped = dump_outputs(args.dump_outputs, batch, r, local, rank, world)
+        log("rank %d: wrote %s to %s" % (rank, dumped, args.dump_outputs))
     # the timed evaluation's own verdicts for this rank's shard prefix (parity below), read back before any other
     # evaluation (serialised, accounting) replaces the resident results
     prefix_status = None
@@ -786,6 +856,10 @@ def main():
                      "per_batch_device_ms": batch_dev,
                      "e2e": e2e},
         }
+        line["full"] = bool(args.full)
+        line["outputs"] = dumped
+        if not args.full:  # no accounting or serialised evaluation ran: there is no roofline to report
+            line["roofline"] = None
         print(json.dumps(line), flush=True)
         if over:  # algorithmic bytes above what HBM can move in the measured time: the accounting is wrong
             log("roofline INVALID: frac > 1 for %s" % over)

@@ -302,6 +302,54 @@ def corpus_ndjson(n, kind="mixed", seed=SEED, edge=False, workers=None, chunk=20
     return b"".join(parts), Gen(seed).ns_labels()
 
 
+def corpus_cache_base(cache_dir, n, kind="mixed", seed=SEED, edge=False, start=0):
+    """path (without extension) of the cache entry of corpus_ndjson(n, kind, seed, edge, start=start)"""
+    import os
+    return os.path.join(cache_dir, "corpus_%s_%d_%x_%d_%d" % (kind, n, seed, int(edge), start))
+
+
+def corpus_is_cached(cache_dir, n, kind="mixed", seed=SEED, edge=False, start=0):
+    import os
+    base = corpus_cache_base(cache_dir, n, kind=kind, seed=seed, edge=edge, start=start)
+    return os.path.exists(base + ".ndjson") and os.path.exists(base + ".nsl.json")
+
+
+def write_corpus_cache(cache_dir, n, kind="mixed", seed=SEED, edge=False, start=0, workers=None, chunk=20000):
+    """Fill the cache entry that cached_corpus(n, kind, seed, edge, cache_dir, start) reads, streaming the chunks of
+    corpus_ndjson to disk as the workers finish them (the same bytes; the corpus is never held in memory whole).
+    Returns the entry's size in bytes."""
+    import multiprocessing as mp
+    import os
+    if start % chunk:
+        raise ValueError("corpus shard start must be a multiple of the chunk size")
+    base = corpus_cache_base(cache_dir, n, kind=kind, seed=seed, edge=edge, start=start)
+    os.makedirs(cache_dir, exist_ok=True)
+    jobs = [(kind, seed, s, min(chunk, start + n - s), edge) for s in range(start, start + n, chunk)]
+    workers = workers or min(len(jobs), int(os.environ.get("OMP_NUM_THREADS", "0")) or os.cpu_count() or 1, 16)
+    tmp = base + ".ndjson.tmp"
+    try:
+        with open(tmp, "wb") as f:
+            if workers <= 1 or len(jobs) == 1:
+                for j in jobs:
+                    f.write(_chunk(j))
+            else:
+                pool = mp.get_context("fork").Pool(workers)
+                try:
+                    for part in pool.imap(_chunk, jobs):
+                        f.write(part)
+                finally:
+                    pool.close()
+                    pool.join()
+            size = f.tell()
+        with open(base + ".nsl.json", "w") as f:
+            json.dump(Gen(seed).ns_labels(), f)
+        os.replace(tmp, base + ".ndjson")
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return size
+
+
 def cached_corpus(n, kind="mixed", seed=SEED, edge=False, cache_dir=None, start=0):
     """corpus_ndjson with an optional on-disk cache (KYV_CORPUS_CACHE): profiler runs reuse the corpus a
     plain run generated, so no worker processes are forked under the profiler."""
@@ -309,8 +357,8 @@ def cached_corpus(n, kind="mixed", seed=SEED, edge=False, cache_dir=None, start=
     cache_dir = cache_dir or os.environ.get("KYV_CORPUS_CACHE")
     if not cache_dir:
         return corpus_ndjson(n, kind=kind, seed=seed, edge=edge, start=start)
-    base = os.path.join(cache_dir, "corpus_%s_%d_%x_%d_%d" % (kind, n, seed, int(edge), start))
-    if os.path.exists(base + ".ndjson") and os.path.exists(base + ".nsl.json"):
+    base = corpus_cache_base(cache_dir, n, kind=kind, seed=seed, edge=edge, start=start)
+    if corpus_is_cached(cache_dir, n, kind=kind, seed=seed, edge=edge, start=start):
         with open(base + ".ndjson", "rb") as f:
             data = f.read()
         with open(base + ".nsl.json") as f:

@@ -7,7 +7,7 @@ R=$PWD
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export KYV_CORPUS_CACHE=/tmp/kyv_corpus_$TAG
-B="--workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-account --no-gather"
+B="--full --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-account --no-gather"
 run() {  # name, env...
   local n=$1; shift
   env "$@" timeout -k 10 300 python3 -u $R/bench.py $B > $OUT/$n.log 2>&1 || { echo "FAIL $n"; tail -5 $OUT/$n.log; exit 1; }

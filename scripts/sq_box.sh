@@ -5,7 +5,7 @@ TAG=${1:-sq}
 R=$PWD
 OUT=$R/gpurun_out/sq_$TAG
 mkdir -p $OUT
-BARGS="--steps 2 --warmup 1 --no-cpu-baseline"
+BARGS="--full --steps 2 --warmup 1 --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 60 rocprofv3 -L > $OUT/counters.txt 2>&1
 timeout -s KILL 240 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/p1 -o run -- python3 $R/bench.py $BARGS > $OUT/p1.log 2>&1 || exit 1
