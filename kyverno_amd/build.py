@@ -6,6 +6,7 @@ import concurrent.futures
 import os
 import subprocess
 import sys
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -42,16 +43,38 @@ def _deps(path, seen=None):
     return seen
 
 
+# A build product's modification time is the moment its build step STARTED (_stamp), not the moment it was written: a
+# kernel translation unit compiles for minutes, and a header saved during that time is not in the object although the
+# object is written after it. Dated by its writing, such an object would pass for fresh, and kernels and host code
+# could be linked that disagree about a struct's layout. The same holds for the library and an object replaced while
+# it links. A slack is taken off the start time for the granularity of the file system's modification times: 50 ms
+# (the kernel's coarse clock), or 2 s where the inputs' times are all whole seconds (a file system that keeps no finer
+# ones). An input saved that shortly before the step starts costs one needless rebuild the next time, no more.
+def _mtime(path):
+    return os.stat(path).st_mtime_ns
+
+
+def _start(inputs):
+    """the time to stamp a product with, taken before its inputs are examined"""
+    coarse = all(_mtime(p) % 10**9 == 0 for p in inputs if os.path.exists(p))
+    return time.time_ns() - (2 * 10**9 if coarse else 50 * 10**6)
+
+
+def _stamp(path, t0):
+    os.utime(path, ns=(t0, t0))
+
+
 def _needs(obj, src):
     if not os.path.exists(obj):
         return True
-    t = os.path.getmtime(obj)
-    return any(os.path.getmtime(d) > t for d in _deps(src))
+    t = _mtime(obj)
+    return any(_mtime(d) > t for d in _deps(src))
 
 
 def _compile(src, obj_dir=OBJ, defines=(), host_flags=()):
     path = os.path.join(CSRC, src)
     obj = os.path.join(obj_dir, src + ".o")
+    t0 = _start(_deps(path))
     if not _needs(obj, path):
         return obj
     cmd = [HIPCC] + COMMON + ["-D" + d for d in defines]
@@ -65,6 +88,7 @@ def _compile(src, obj_dir=OBJ, defines=(), host_flags=()):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("compile failed: %s\n%s" % (" ".join(cmd), r.stderr[-6000:]))
+    _stamp(obj, t0)
     return obj
 
 
@@ -75,12 +99,14 @@ def build(verbose=False, lib=LIB, defines=(), obj_dir=OBJ, host_flags=(), link_f
     srcs = HOST_SRCS + HIP_SRCS
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(s, obj_dir, defines, host_flags), srcs))
-    if not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
+    t0 = _start(objs)
+    if not os.path.exists(lib) or any(_mtime(o) > _mtime(lib) for o in objs):
         cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs + list(link_flags) + \
               ["-lpthread", "-L/opt/rocm/lib", "-lhiprtc", "-lrccl", "-ldl"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
+        _stamp(lib, t0)
     if verbose:
         print("built", lib)
     return lib
