@@ -178,6 +178,25 @@ int kyv_batch_build(const kyv_ruleset* rs, const char* resources_json, size_t le
 void kyv_batch_free(kyv_batch* b);
 uint32_t kyv_batch_num_resources(const kyv_batch* b);
 int kyv_batch_stats_get(const kyv_batch* b, kyv_batch_stats* out);
+/* What the flattener tells the compiled kernels about whole match waves (diagnostics, read-only). A match wave is 64
+ * consecutive resources of the batch's kind-major order; order[p] = index in the caller's input of the resource at
+ * position p. Every buffer may be NULL (its capacity is then ignored); a non-NULL buffer that is too small fails
+ * with KYV_EINVAL. Capacities count elements of the buffer's type.
+ *   facts [waves]         all-maps bits of each wave: bit j set = every element of the wave's lists at maps[j] is a
+ *                         non-null object. With KYV_FACT_MAPS=0 in the environment the batch reports "nothing known"
+ *                         (every bit clear), to this call as to the kernels.
+ *   hot   [resources][4]  the hot header row of each resource: root node offset, node count, flags, kind class
+ *   bits                  JSON {"maps": [path, ...]}: what each bit stands for; path segments are JSON strings in a
+ *                         list, "[*]" the elements of a list
+ * bits_len receives the JSON's full length. */
+typedef struct kyv_wave_facts_out {
+  uint32_t* facts; size_t facts_cap;
+  uint32_t* hot; size_t hot_cap;
+  uint32_t* order; size_t order_cap;
+  char* bits; size_t bits_cap;
+  size_t bits_len;
+} kyv_wave_facts_out;
+int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out);
 
 /* ---- evaluation: engine.Validate over every (resource, rule) pair ---- */
 int kyv_eval(const kyv_ruleset* rs, const kyv_batch* b, const kyv_eval_opts* opts, kyv_results** out);

@@ -65,8 +65,14 @@ EXPORTS = [
     "kyv_results_texts", "kyv_results_phase_ms", "kyv_results_alg_bytes_phase", "kyv_results_alg_bytes_class", "kyv_batch_export_status", "kyv_batch_copy_status",
     "kyv_batch_export_failures", "kyv_comm_unique_id", "kyv_comm_init", "kyv_comm_free", "kyv_comm_gather_results",
     "kyv_comm_gathered_status", "kyv_comm_gathered_failures", "kyv_comm_gather_report", "kyv_comm_reduce_counts", "kyv_results_batch_ms",
-    "kyv_calibrate_fetch",
+    "kyv_calibrate_fetch", "kyv_batch_wave_facts",
 ]
+
+
+class WaveFactsOut(ctypes.Structure):
+    _fields_ = [("facts", ctypes.c_void_p), ("facts_cap", ctypes.c_size_t), ("hot", ctypes.c_void_p),
+                ("hot_cap", ctypes.c_size_t), ("order", ctypes.c_void_p), ("order_cap", ctypes.c_size_t),
+                ("bits", ctypes.c_void_p), ("bits_cap", ctypes.c_size_t), ("bits_len", ctypes.c_size_t)]
 
 
 class GatherStats(ctypes.Structure):
@@ -141,6 +147,7 @@ def lib():
     L.kyv_batch_num_resources.argtypes = [vp]
     L.kyv_batch_num_resources.restype = u32
     L.kyv_batch_stats_get.argtypes = [vp, ctypes.POINTER(BatchStats)]
+    L.kyv_batch_wave_facts.argtypes = [vp, ctypes.POINTER(WaveFactsOut)]
     L.kyv_eval.argtypes = [vp, vp, ctypes.POINTER(EvalOpts), ctypes.POINTER(vp)]
     L.kyv_results_free.argtypes = [vp]
     L.kyv_results_status.argtypes = [vp, ctypes.c_void_p, sz]

@@ -1046,6 +1046,17 @@ Batch* build_batch(const Ruleset* rs, const char* json, size_t len, const char* 
     order_by_kind(*b);
     phase("kind-order");
     resolve_path_columns(*b, T);
+    // hot header plane (kyv_layout.h HotHdr): written last, the headers are final from here on
+    b->hot.resize(b->hdr.size());
+    {
+      const size_t n = b->hdr.size(), per = (size_t)1 << 16;
+      parallel_for((n + per - 1) / per, T, [&](size_t k) {
+        for (size_t r = k * per, e = std::min(n, r + per); r < e; r++) {
+          const ResHeader& h = b->hdr[r];
+          b->hot[r] = HotHdr{h.root, h.nnodes, h.flags, h.kclass};
+        }
+      });
+    }
     phase("path-cols");
     // to_upper on the dictionary (round 6, kyverno functions.go:681-689 strings.ToUpper): the upper-case form of every
     // string that can reach a to_upper argument -- the values of the argument's field chain (its path column, filled
@@ -1159,6 +1170,9 @@ struct Resolver {
   uint64_t* colv;            // nullptr in the counting pass
   const uint32_t* col_off;
   uint32_t* next;            // next free row per row space
+  // per-wave facts of the resource being resolved (kyv_layout.h WaveFacts): bit of a row space, -1 none
+  const int8_t* space_bit;
+  uint32_t notmaps = 0;
   uint64_t entry(uint32_t x) const {
     return ((uint64_t)R[x].a << 32) | ((uint64_t)node_type(R[x]) << COL_TYPE_SHIFT) | x;
   }
@@ -1205,6 +1219,9 @@ struct Resolver {
         const size_t self = col_off[rs.trie[T.star].col];
         for (uint32_t i = 0; i < mn.b; i++) colv[self + base + i] = entry(mn.a + i);
       }
+      if (space_bit[space] >= 0)
+        for (uint32_t i = 0; i < mn.b; i++)
+          if (node_type(R[mn.a + i]) != N_MAP) notmaps |= 1u << space_bit[space];
       for (uint32_t i = 0; i < mn.b; i++) go(mn.a + i, T.star, base + i);
     }
   }
@@ -1218,7 +1235,10 @@ void resolve_path_columns(Batch& b, int threads) {
   b.rs_rows.assign(nsp, 0);
   b.col_off.assign(rs.ncols, 0);
   b.colv.clear();
+  b.facts.assign((n + 63) / 64, WaveFacts{0u});  // .maps collects "some element is not an object" until the end
   if (rs.ncols == 0 || n == 0) return;
+  std::vector<int8_t> space_bit(nsp, -1);
+  for (size_t i = 0; i < rs.fact_spaces.size(); i++) space_bit[rs.fact_spaces[i]] = (int8_t)i;
   int T = std::max(1, threads);
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> kids(rs.trie.size());
   for (size_t t = 0; t < rs.trie.size(); t++) {
@@ -1238,8 +1258,11 @@ void resolve_path_columns(Batch& b, int threads) {
         for (size_t r = r0; r < r1; r++) {
           ResHeader& h = b.hdr[r];
           if (!eligible(h)) continue;
-          Resolver rv{rs, kids, b.nodes.data() + h.root, fill ? b.colv.data() : nullptr, b.col_off.data(), nexts[c].data()};
+          Resolver rv{rs, kids, b.nodes.data() + h.root, fill ? b.colv.data() : nullptr, b.col_off.data(), nexts[c].data(),
+                      space_bit.data()};
           rv.go(0, 0, (uint32_t)r);
+          // a wave's row is shared by the chunks (worker threads) whose resource ranges meet inside it: atomic OR
+          if (fill && rv.notmaps) __atomic_fetch_or(&b.facts[r / 64].maps, rv.notmaps, __ATOMIC_RELAXED);
         }
       }
     };
@@ -1281,6 +1304,13 @@ void resolve_path_columns(Batch& b, int threads) {
   run(true, base);
   // resources too large for column encoding: pattern pairs fall back (RF_MAGIC), so no column is read
   for (auto& h : b.hdr) if (!eligible(h)) h.flags |= RF_MAGIC;
+  const uint32_t defined = rs.fact_spaces.size() >= 32 ? 0xFFFFFFFFu : (1u << rs.fact_spaces.size()) - 1u;
+  for (auto& f : b.facts) f.maps = ~f.maps & defined;
+}
+
+uint32_t wave_maps_mask() {
+  const char* e = getenv("KYV_FACT_MAPS");
+  return e && atoi(e) == 0 ? 0u : 0xFFFFFFFFu;
 }
 
 std::string format_path(const Ruleset& rs, const Batch& b, uint32_t tmpl, const uint16_t* idx, const uint32_t* key) {

@@ -224,11 +224,67 @@ int kyv_batch_stats_get(const kyv_batch* b, kyv_batch_stats* out) {
   out->nodes = x.nodes.size();
   out->strings = x.dict.strs.size();
   out->heap_bytes = x.heap.size();
-  out->device_bytes = x.nodes.size() * sizeof(Node) + x.hdr.size() * sizeof(ResHeader) + x.heap.size() +
+  out->device_bytes = x.nodes.size() * sizeof(Node) + x.hdr.size() * sizeof(ResHeader) + x.hot.size() * sizeof(HotHdr) + x.heap.size() +
                       x.dict.strs.size() * (4 + 4 + 4 + 8 + 16 + 8) + x.faux.size() * sizeof(FloatAux) +
                       x.colv.size() * sizeof(uint64_t) + x.col_off.size() * 4 + x.gate.size() * 4 +
                       (x.str_upper.size() + x.str_rx.size()) * 4;
   return KYV_OK;
+}
+
+// what the bits of a WaveFacts row stand for, as JSON (kyvgpu.h kyv_batch_wave_facts): the trie paths of
+// Ruleset::fact_spaces
+static std::string wave_fact_bits_json(const Ruleset& rs) {
+  std::vector<std::string> space_path(rs.nrowspaces);
+  auto quote = [](const std::string& s) {
+    std::string o = "\"";
+    for (unsigned char ch : s) {
+      if (ch == '"' || ch == '\\') { o += '\\'; o += (char)ch; }
+      else if (ch < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", ch); o += b; }
+      else o += (char)ch;
+    }
+    return o + "\"";
+  };
+  std::function<void(uint32_t, const std::string&)> go = [&](uint32_t t, const std::string& path) {
+    const Ruleset::TrieNode& T = rs.trie[t];
+    if (T.star != NONE) {
+      const std::string p = path + (path.empty() ? "" : ",") + "\"[*]\"";
+      space_path[rs.trie[T.star].rowspace] = p;
+      go(T.star, p);
+    }
+    for (const auto& kv : T.kids) go(kv.second, path + (path.empty() ? "" : ",") + quote(rs.dict.strs[kv.first]));
+  };
+  if (!rs.trie.empty()) go(0, "");
+  std::string js = "{\"maps\":[";
+  for (size_t i = 0; i < rs.fact_spaces.size(); i++) js += (i ? ",[" : "[") + space_path[rs.fact_spaces[i]] + "]";
+  return js + "]}";
+}
+
+int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out) {
+  if (!b || !out) return fail(KYV_EINVAL, "null argument");
+  try {
+    const Batch& x = *b->b;
+    const size_t n = x.hdr.size(), nw = (n + 63) / 64;
+    if ((out->facts && out->facts_cap < nw) || (out->hot && out->hot_cap < 4 * n) || (out->order && out->order_cap < n))
+      return fail(KYV_EINVAL, "buffer too small");
+    if (out->facts) {
+      const uint32_t m = wave_maps_mask();
+      for (size_t w = 0; w < nw; w++) out->facts[w] = (w < x.facts.size() ? x.facts[w].maps : 0u) & m;
+    }
+    if (out->hot) {
+      if (x.hot.size() != n) return fail(KYV_EINTERNAL, "batch has no hot header plane");
+      memcpy(out->hot, x.hot.data(), n * sizeof(HotHdr));
+    }
+    if (out->order) for (size_t p = 0; p < n; p++) out->order[p] = p < x.order.size() ? x.order[p] : (uint32_t)p;
+    const std::string js = wave_fact_bits_json(*x.rs);
+    out->bits_len = js.size();
+    if (out->bits) {
+      if (out->bits_cap < js.size() + 1) return fail(KYV_EINVAL, "buffer too small");
+      memcpy(out->bits, js.c_str(), js.size() + 1);
+    }
+    return KYV_OK;
+  } catch (std::exception& e) {
+    return fail(KYV_EINTERNAL, e.what());
+  }
 }
 
 int kyv_eval(const kyv_ruleset* rs, const kyv_batch* b, const kyv_eval_opts* opts, kyv_results** out) {

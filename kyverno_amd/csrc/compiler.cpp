@@ -2682,6 +2682,32 @@ void build_path_trie(Ruleset& rs) {
     for (auto& rd : rs.rules) tb.pss_rule(rd);
   // entries of pnodes that conflicted after their first visit assigned columns: clear the whole subtree
   // (a conflicting subtree is walked with t == NONE, which already cleared its entries' columns)
+  assign_wave_facts(rs);
+}
+
+// Per-wave facts (round 7, Batch::facts): what the flattener can tell the walk about a whole match wave of 64
+// resources, so that a load whose result is known when the batch is built is not issued.
+//   fact_spaces: the row spaces of the elements of array-of-maps patterns whose element pattern is a map, in
+//                ascending order, at most FACT_BITS; all-maps bit j of a wave = every element of every list of row
+//                space fact_spaces[j] owned by the wave's resources is an object (the element's self column then
+//                says nothing the walk does not know: type N_MAP, node = first element + i)
+// A row space beyond the budget has no bit: its self column is always loaded.
+void assign_wave_facts(Ruleset& rs) {
+  rs.fact_spaces.clear();
+  std::set<uint32_t> spaces;
+  for (size_t pn = 0; pn < rs.pnodes.size(); pn++) {
+    const PNode& P = rs.pnodes[pn];
+    if (rs.pn_self[pn] == NONE) continue;
+    bool map_child = false;
+    if (P.kind == P_ARR_MAPS) map_child = P.first < rs.pnodes.size() && rs.pnodes[P.first].kind == P_MAP;
+    else if (P.kind == P_ARR_POS)
+      for (uint32_t i = 0; i < P.n; i++) {
+        const uint32_t ch = rs.pool[P.first + i];
+        map_child = map_child || (ch < rs.pnodes.size() && rs.pnodes[ch].kind == P_MAP);
+      }
+    if (map_child) spaces.insert(rs.col_rowspace[rs.pn_self[pn]]);
+  }
+  for (uint32_t s2 : spaces) if (rs.fact_spaces.size() < FACT_BITS) rs.fact_spaces.push_back(s2);
 }
 
 }  // namespace kyv

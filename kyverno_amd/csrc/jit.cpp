@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -301,7 +302,17 @@ struct Gen {
                 << 16u * P.level << ");\n";
           out << "    { const uint32_t er = eb == NONE ? NONE : eb + " << i << ";\n"
               << "      " << preload(child, "pe", "er") << "\n";
-          if (self != NONE)
+          // all-maps fact of the elements' row space (kyv_layout.h WaveFacts::maps): every element of the wave's lists is an
+          // object, so an element with a map pattern needs nothing of its self entry -- type N_MAP, node = the array's
+          // first element + i (the entry's `a` word is not read by a map pattern); the load is skipped as its own "no
+          // row" case (no branch around it: it stays in the memory round of the element's column preload)
+          const auto fs = self == NONE ? rs.fact_spaces.end()
+                                       : std::find(rs.fact_spaces.begin(), rs.fact_spaces.end(), rs.col_rowspace[self]);
+          if (self != NONE && fs != rs.fact_spaces.end() && rs.pnodes[child].kind == P_MAP)
+            out << "      const bool em = ((w.am >> " << u((uint32_t)(fs - rs.fact_spaces.begin())) << ") & 1u) != 0u;\n"
+                   "      uint32_t et, ea; uint32_t ei = jdec(jself(w, " << u(self) << ", em ? NONE : er), &et, &ea);\n"
+                   "      if (ei == NONE) { ei = aa + " << i << "; et = (em && er != NONE) ? (uint32_t)N_MAP : T_UNK; }\n";
+          else if (self != NONE)
             out << "      uint32_t et, ea; uint32_t ei = jdec(jself(w, " << u(self) << ", er), &et, &ea);\n"
                    "      if (ei == NONE) { ei = aa + " << i << "; et = T_UNK; }\n";
           else
@@ -318,6 +329,8 @@ struct Gen {
         const size_t S = scope_of[P.first].size() + (self != NONE ? 1 : 0);
         const size_t K = P.kind == P_ARR_MAPS && batch_max > 1 && S > 0 ? std::max<size_t>(1, std::min<size_t>(batch_max, 8 / S)) : 1;
         if (P.kind == P_ARR_MAPS && K > 1) {
+          // (KYV_JIT_BATCH experiments only: this batched form loads every element's self entry and does not use the
+          // all-maps fact; the default K == 1 form below does)
           out << "  for (uint32_t i0 = 0; i0 < cnt; i0 += " << K << "u) {\n";
           for (size_t q = 0; q < K; q++) {
             const std::string Q = std::to_string(q);
@@ -379,6 +392,7 @@ struct Gen {
     if (slot_alen[pn] >= 0)
       out << "  if (rt == N_ARR && (uint32_t)(pc[" << slot_alen[pn] << "] >> 32) != NONE) {\n"
              "    cnt = (uint32_t)pc[" << slot_alen[pn] << "]; eb = (uint32_t)(pc[" << slot_alen[pn] << "] >> 32);\n"
+             "    aa = ra;  // the array's first element: its column entry's `a` word\n"
              "  } else\n";
     out << "  { const Node a = gnode(w.R + rn);\n"
            "    if (node_type(a) != N_ARR) return mkerr(EC_NONE, 0, " << T << ");\n"
@@ -432,7 +446,7 @@ struct Gen {
       // decided from the header flags the flattener computed for that position (same order as expand_meta:
       // absent/null metadata, non-object, anchor-like keys, labels / annotations that are not objects of strings)
       const uint32_t sh = meta_pos[pn] == 0 ? RF_META_SHIFT : meta_pos[pn] == 1 ? RF_TMETA1_SHIFT : RF_TMETA2_SHIFT;
-      out << "  { const uint32_t hf = gld32(&w.hp->flags); KYV_ACCT_ADD(0, 4);\n"
+      out << "  { const uint32_t hf = ghot_flags(w.v, w.hp);\n"
              "    if (!(hf & (1u << " << sh << "))) {\n"
              "      if (hf & (2u << " << sh << ")) { w.ost = ST_PANIC; return ok_ret(); }\n"
              "      if (hf & RF_ANCHORISH) { w.ost = ST_FALLBACK; return ok_ret(); }\n";
@@ -1216,10 +1230,9 @@ struct CondGen {
     if (kind_only(rd)) out << "  // match block = the kind gate (checked by the kernel)\n";
     else out << "  { const int m = jc_match(v, r, " << u(k) << "); if (m >= 0) return (uint8_t)m; }\n";
     out << "#ifdef KYV_EXP_JC_EMPTY\n  return ST_PASS;\n#endif\n";
-    out << "  const ResHeader& h = v.hdr[r];\n"
-        << "  KYV_ACCT_ADD(0, 8);  // header: node count, root\n"
-        << "  if (h.nnodes >= (1u << COL_TYPE_SHIFT)) return ST_FALLBACK;  // no path columns for this resource\n"
-        << "  const Node* R = v.nodes + h.root;\n"
+    // (the header's root and node count come with the wave's hot rows: the kernel loaded them once for all its rules)
+    out << "  if (hnn >= (1u << COL_TYPE_SHIFT)) return ST_FALLBACK;  // no path columns for this resource\n"
+        << "  const Node* R = v.nodes + hroot;\n"
         << "  const uint32_t ei = NONE, et = T_UNK, ea = 0u, erow = NONE;\n";
     const std::string args = "(v, R, r, ei, et, ea, erow, L)";
     if (rd.pre != NONE) {
@@ -1255,7 +1268,7 @@ struct CondGen {
     const std::string b = out.str();
     out.swap(save);
     // inlined into its rule's kernel (kyv_jit_cond_<k>): no call frame (callee-saved registers in scratch memory)
-    defs << "static __device__ __forceinline__ uint8_t jr" << k << "(const View& v, uint32_t r, uint32_t* L) {\n" << b << "}\n";
+    defs << "static __device__ __forceinline__ uint8_t jr" << k << "(const View& v, uint32_t r, uint32_t hroot, uint32_t hnn, uint32_t* L) {\n" << b << "}\n";
   }
 };
 
@@ -1587,11 +1600,11 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
       if (rep_of[r] == r)  // one root function per pattern shape
       src << "static __device__ __forceinline__ void root" << r
           << "(const View& v, const Node* R, const ResHeader* hp, uint32_t row, uint32_t mbase, bool rootmap, bool walk,\n"
-             "    PatOut& out) {\n"
+             "    PatOut& out, const uint32_t am) {\n"
              "  " << g.preload(r, "pc", "row", "jc_col(v, ") << "\n"
              "  if (!walk) return;\n"
              "#ifdef KYV_EXP_JIT_PRELOAD\n  { uint64_t x = 0; for (auto q : pc) x ^= q; out.status = x == 0x123456789ull ? ST_FAIL : ST_PASS; return; }\n#endif\n"
-             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE};\n"
+             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am};\n"
              "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
              "  jfinish(w, r, out);\n"
              "}\n";
@@ -1656,7 +1669,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         const auto& L = g.scope_of[r];
         src << "static __device__ __forceinline__ void rootc" << r << "_" << gi
             << "(const View& v, const Node* R, const ResHeader* hp, uint32_t row, uint32_t mbase, bool rootmap, bool walk,\n"
-               "    PatOut& out, const uint64_t* jcc) {\n"
+               "    PatOut& out, const uint64_t* jcc, const uint32_t am) {\n"
                "  const uint32_t lane = threadIdx.x & 63u;\n"
                "  (void)lane;\n"
                "  uint64_t pc[" << std::max<size_t>(1, L.size()) << "];";
@@ -1667,7 +1680,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         }
         src << "\n"
                "  if (!walk) return;\n"
-               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE};\n"
+               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am};\n"
                "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
                "  jfinish(w, r, out);\n"
                "}\n";
@@ -1685,6 +1698,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     }
     src << "struct JitWalker" << gi << " {\n"
            "  bool rootmap;\n"
+           "  uint32_t am;\n"
            "  __device__ __forceinline__ void run(const View& v, uint32_t root, bool walk, const Node* R, const ResHeader* hp,\n"
            "                                     uint32_t row, const RuleDesc& rd, PatOut& out) {\n"
            "    out.status = ST_NONE; out.idx = 0; out.tmpl = NONE; out.key0 = NONE; out.key1 = NONE;\n"
@@ -1700,12 +1714,12 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     if (roots.size() <= 256) {
       for (auto& br : by_rep) {
         for (uint32_t r : br.second) src << "      case " << r << "u:";
-        src << " root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out); break;\n";
+        src << " root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am); break;\n";
       }
     } else {
       uint32_t si = 0;
       for (auto& br : by_rep) {
-        src << "      case " << si++ << "u: root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out); break;\n";
+        src << "      case " << si++ << "u: root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am); break;\n";
       }
     }
     src << "      default: if (walk) out.status = ST_FALLBACK;\n"
@@ -1737,13 +1751,14 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
           if (fold_mode == 2 ? pi + 1 == nparts : j % nparts == pi) conds.push_back(folded[j]);
       src << "struct " << sname << " {\n"
              "  __device__ __forceinline__ void run(const View& v, const DevOut& o, uint32_t nwaves, uint32_t w, uint32_t r,\n"
-             "                                     bool active, uint32_t hflags, uint32_t hroot, const uint32_t* gw) {\n"
+             "                                     bool active, uint32_t hflags, uint32_t hroot, uint32_t hnn, const uint32_t* gw) {\n"
              "    const uint32_t lane = threadIdx.x & 63u;\n"
              "    const Node* R = v.nodes + hroot;\n"
              "    const ResHeader* hp = v.hdr + r;\n"
              "    const uint32_t row = r < v.nres ? r : NONE;\n"
              "    const bool rootmap = (hflags & RF_ROOT_MAP) != 0;\n"
-             "    (void)lane; (void)hp; (void)rootmap;\n";
+             "    const uint32_t am = wave_maps(v, w);\n"
+             "    (void)lane; (void)hp; (void)rootmap; (void)hnn; (void)am;\n";
       if (!conds.empty()) src << "    __shared__ uint32_t jl[" << jc_lds << "];\n";
       if (ncslots) {
         // the part's cached root columns, each loaded by the lanes some rule of this part (in this rule slice) walks
@@ -1792,10 +1807,10 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         const uint32_t root = rule_roots[i].second[a];
         if (ncslots)
           src << "            case " << a << "u: rootc" << rep_of[root] << "_" << gi << "(vl, R, hp, row, " << Gen::u(rd.meta_sites)
-              << ", rootmap, wk, po, jcc); break;\n";
+              << ", rootmap, wk, po, jcc, am); break;\n";
         else
           src << "            case " << a << "u: root" << rep_of[root] << "(vl, R, hp, row, " << Gen::u(rd.meta_sites)
-              << ", rootmap, wk, po); break;\n";
+              << ", rootmap, wk, po, am); break;\n";
       }
       src << "            default: break;\n"
              "          }\n"
@@ -1815,7 +1830,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
                "      const bool gated = active && ((gw[" << k / 32 << "] >> " << k % 32 << "u) & 1u);\n"
                "      if (__ballot(gated)) {\n"
                "        uint8_t st = ST_NONE;\n"
-               "        if (gated) st = jr" << k << "(KYV_RULE_VIEW(v), r, jl + lane);\n"
+               "        if (gated) st = jr" << k << "(KYV_RULE_VIEW(v), r, hroot, hnn, jl + lane);\n"
                "        if (gated && st != ST_NONE) { o.status[(size_t)" << K << " * v.nres + r] = st; KYV_ACCT_ADD(1, 1); }\n"
                "      }\n"
                "    }\n";
@@ -1831,14 +1846,14 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     if (nparts > 1 && getenv("KYV_FUSED_MERGE") && atoi(getenv("KYV_FUSED_MERGE")) != 0) {
       src << "struct JitFusedM" << gi << " {\n"
              "  __device__ __forceinline__ void run(const View& v, const DevOut& o, uint32_t nwaves, uint32_t w, uint32_t r,\n"
-             "                                     bool active, uint32_t hflags, uint32_t hroot, const uint32_t* gw) {\n";
+             "                                     bool active, uint32_t hflags, uint32_t hroot, uint32_t hnn, const uint32_t* gw) {\n";
       for (size_t pi = 0; pi < nparts; pi++) {
         const std::string sname = "JitFused" + std::to_string(gi) + (pi ? "p" + std::to_string(pi) : std::string());
         src << "    {\n"
                "      uint32_t r2 = r, h2 = hroot;\n"
                "      asm volatile(\"\" : \"+v\"(r2), \"+v\"(h2));\n"
                "      " << sname << " f;\n"
-               "      f.run(v, o, nwaves, w, r2, active, hflags, h2, gw);\n"
+               "      f.run(v, o, nwaves, w, r2, active, hflags, h2, hnn, gw);\n"
                "    }\n";
       }
       src << "  }\n"
@@ -1873,7 +1888,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     // every root function a shape needs is already in the source (its users are covered rules of some group)
     src << "struct JitShapes {\n"
            "  __device__ __forceinline__ void run(const View& v, const ShapeOut& so, uint32_t r, bool active, uint32_t hflags,\n"
-           "                                     uint32_t hroot, uint32_t cls) {\n"
+           "                                     uint32_t hroot, uint32_t cls, const uint32_t am) {\n"
            "    const Node* R = v.nodes + hroot;\n"
            "    const ResHeader* hp = v.hdr + r;\n"
            "    const uint32_t row = r < v.nres ? r : NONE;\n"
@@ -1888,7 +1903,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
              "        ShapeSink sink{so.rec + (size_t)" << S << " * v.nres + r};\n"
              "        uint8_t st = pair_walk_alts(true, 1u, gated && !magic, r, 0u, sink, [&](uint32_t, bool wk, PatOut& po) {\n"
              "          po.status = ST_NONE; po.idx = 0; po.tmpl = NONE; po.key0 = NONE; po.key1 = NONE;\n"
-             "          root" << shape_list[si].first << "(v, R, hp, row, " << Gen::u(shape_list[si].second) << ", rootmap, wk, po);\n"
+             "          root" << shape_list[si].first << "(v, R, hp, row, " << Gen::u(shape_list[si].second) << ", rootmap, wk, po, am);\n"
              "        });\n"
              "        if (magic) st = ST_FALLBACK;\n"
              "        if (gated) { so.st[(size_t)" << S << " * v.nres + r] = st; KYV_ACCT_ADD(1, 1); }\n"
@@ -1927,7 +1942,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
              "    const bool gated = " << on << "((gw[" << k / 32 << "u] >> " << k % 32 << "u) & 1u);\n"
              "    if (__ballot(gated)) {\n"
              "      uint8_t st = kyv::ST_NONE;\n"
-             "      if (gated) st = kyv::jr" << k << "(KYV_RULE_VIEW(v), r, jl + lane);\n"
+             "      if (gated) st = kyv::jr" << k << "(KYV_RULE_VIEW(v), r, hh.root, hh.nnodes, jl + lane);\n"
              "      if (gated && st != kyv::ST_NONE) { o.status[(size_t)" << k << "u * v.nres + r] = st; KYV_ACCT_ADD(1, 1); }\n"
              "    }\n"
              "  }\n";
@@ -1939,8 +1954,9 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
                "  __shared__ uint32_t jl[" << lds << "];\n"
                "  const kyv::View& v = *vp;\n"
                "  const uint32_t lane = threadIdx.x, r = (w0 + blockIdx.x) * 64u + lane;\n"
-               "  const uint32_t* gw = r < v.nres ? v.gate + (size_t)v.hdr[r].kclass * v.gate_words : nullptr;\n"
-               "  if (r < v.nres) KYV_ACCT_ADD(0, 4);  // header: kind class\n";
+               "  kyv::HotHdr hh{0u, 0u, 0u, 0u};\n"
+               "  if (r < v.nres) hh = kyv::ghot(v, r);  // header: kind class, and root and node count for the rules\n"
+               "  const uint32_t* gw = r < v.nres ? v.gate + (size_t)hh.kclass * v.gate_words : nullptr;\n";
         for (size_t i = 0; i < grp.size(); i++) member(grp[i], "gw && (mask & " + std::to_string(1u << i) + "u) && ");
         src << "}\n";
       }
@@ -1951,8 +1967,9 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
                "  __shared__ uint32_t jl[" << lds << "];\n"
                "  const kyv::View& v = *vp;\n"
                "  const uint32_t lane = threadIdx.x, r = (w0 + blockIdx.x) * 64u + lane;\n"
-               "  const uint32_t* gw = r < v.nres ? v.gate + (size_t)v.hdr[r].kclass * v.gate_words : nullptr;\n"
-               "  if (r < v.nres) KYV_ACCT_ADD(0, 4);  // header: kind class\n";
+               "  kyv::HotHdr hh{0u, 0u, 0u, 0u};\n"
+               "  if (r < v.nres) hh = kyv::ghot(v, r);  // header: kind class, and root and node count for the rules\n"
+               "  const uint32_t* gw = r < v.nres ? v.gate + (size_t)hh.kclass * v.gate_words : nullptr;\n";
         member(k, "gw && ");
         src << "}\n";
       }
@@ -1965,7 +1982,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     src << "extern \"C\" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu("
         << (gwpe[gi] == -2 ? "KYV_JIT_WPE_LIGHT" : "KYV_JIT_WPE") << ")))\n"
            "kyv_jit_walk_" << gi << "(const kyv::View* __restrict__ vp, kyv::DevOut o, kyv::WorkLists wl, kyv::ChunkMap cm) {\n"
-           "  kyv::JitWalker" << gi << " wk{false};\n"
+           "  kyv::JitWalker" << gi << " wk{false, 0u};\n"
            "  kyv::walk_chunks(*vp, o, wl, cm, wk);\n"
            "}\n";
   // fused kernels: one workgroup (one wave) per match wave of the batch. A fused kernel holds every direct rule of its

@@ -414,6 +414,10 @@ struct DeviceResults {
   hipStream_t wstream = nullptr;
   hipEvent_t wfork = nullptr, wjoin = nullptr;
   View* view = nullptr;  // device copy of the View the kernel reads
+  // its fields the run-time switches set (KYV_HOTHDR, KYV_FACT_*): a later evaluation under other settings uploads
+  // the View again
+  const HotHdr* view_hot = nullptr;
+  uint32_t view_fact_and = 0;
   // pattern-shape tables (kyv_jit_shapes, round 5): [shape][res] verdict bytes and records, the per-class shape gate
   uint8_t* shape_st = nullptr;
   FailRec* shape_rec = nullptr;
@@ -452,7 +456,7 @@ struct DevBatch {
   DeviceResults* out = nullptr;  // result buffers + stream, resident across evaluations
   uint8_t* base = nullptr;
   size_t bytes = 0;
-  size_t o_nodes, o_hdr, o_faux, o_soff, o_slen, o_sflags, o_sdur, o_sqty, o_sf64, o_heap, o_nsloff, o_nslkv, o_gate,
+  size_t o_nodes, o_hdr, o_hot, o_facts, o_faux, o_soff, o_slen, o_sflags, o_sdur, o_sqty, o_sf64, o_heap, o_nsloff, o_nslkv, o_gate,
       o_colv, o_coloff, o_pe, o_supper = SIZE_MAX, o_srx = SIZE_MAX;
   uint32_t* gmask = nullptr;   // [string][words] glob-mask bits, computed on the device once per batch
   uint32_t gmask_words = 0;
@@ -502,6 +506,8 @@ static DevBatch* upload_batch(const Batch& b, int device) {
   Packer p;
   d->o_nodes = p.add(b.nodes);
   d->o_hdr = p.add(b.hdr);
+  d->o_hot = p.add(b.hot);
+  d->o_facts = p.add(b.facts);
   d->o_faux = p.add(b.faux);
   d->o_soff = p.add(b.str_off);
   d->o_slen = p.add(b.str_len);
@@ -529,12 +535,21 @@ static DevBatch* upload_batch(const Batch& b, int device) {
   return d;
 }
 
+// KYV_HOTHDR=0: the kernels read the header words from hdr[] as before round 7 (View::hot = nullptr; a run-time
+// switch of the evaluation, no recompile: A/B runs and the parity tests compare both in one build)
+static bool hot_plane_on() {
+  const char* e = getenv("KYV_HOTHDR");
+  return !e || atoi(e) != 0;
+}
+
 static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, const DevRuleset* dr, const uint8_t* bbase,
                       const DevBatch* db) {
   View v{};
   if (db) {
     v.nodes = (const Node*)(bbase + db->o_nodes);
     v.hdr = (const ResHeader*)(bbase + db->o_hdr);
+    v.hot = hot_plane_on() && b.hot.size() == b.hdr.size() ? (const HotHdr*)(bbase + db->o_hot) : nullptr;
+    v.facts = b.facts.size() == (b.hdr.size() + 63) / 64 ? (const WaveFacts*)(bbase + db->o_facts) : nullptr;
     v.faux = (const FloatAux*)(bbase + db->o_faux);
     v.str_off = (const uint32_t*)(bbase + db->o_soff);
     v.str_len = (const uint32_t*)(bbase + db->o_slen);
@@ -556,6 +571,8 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
     v.str_gmask = nullptr;
     v.gmask_words = 0;
     v.nodes = b.nodes.data(); v.hdr = b.hdr.data(); v.faux = b.faux.data();
+    v.hot = hot_plane_on() && b.hot.size() == b.hdr.size() ? b.hot.data() : nullptr;
+    v.facts = b.facts.size() == (b.hdr.size() + 63) / 64 ? b.facts.data() : nullptr;
     v.str_off = b.str_off.data(); v.str_len = b.str_len.data(); v.str_flags = b.str_flags.data();
     v.str_dur = b.str_dur.data(); v.str_qty = b.str_qty.data(); v.str_f64 = b.str_f64.data();
     v.heap = b.heap.data(); v.nsl_off = b.nsl_off.data(); v.nsl_kv = b.nsl_kv.data();
@@ -567,6 +584,7 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
   }
   v.gate_words = b.gate_words;
   v.nres = (uint32_t)b.hdr.size();
+  v.fact_and = wave_maps_mask();
   v.nrules = (uint32_t)rs.rules.size();
   if (dr) {
     v.rules = (const RuleDesc*)(rbase + dr->o_rules);
@@ -1779,6 +1797,7 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     stream_get(&d.stream, &d.e0, &d.e1);
     HIP_OK(dmalloc(&d.view, sizeof(View)));
     HIP_OK(hipMemcpy(d.view, &v, sizeof(View), hipMemcpyHostToDevice));
+    d.view_hot = v.hot; d.view_fact_and = v.fact_and;
     d.wl.nwaves = (uint32_t)((nres + WAVE - 1) / WAVE);
     const size_t nwv = d.wl.nwaves;
     // rule slices: consecutive rules while their walk buffers fit the budget (and every slice-local index fits 32 bits)
@@ -1849,6 +1868,11 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     db->out = dd;
   }
   DeviceResults& d = *db->out;
+  if (d.view_hot != v.hot || d.view_fact_and != v.fact_and) {
+    // (no evaluation of this batch is in flight here: each one ends synchronised with its streams)
+    HIP_OK(hipMemcpy(d.view, &v, sizeof(View), hipMemcpyHostToDevice));
+    d.view_hot = v.hot; d.view_fact_and = v.fact_and;
+  }
   hipStream_t stream = d.stream;
   const bool use_jit = jit_mode == JIT_ON || (jit_mode == JIT_AUTO && nres >= JIT_AUTO_MIN_RESOURCES);
   const bool jit = use_jit && ensure_jit(mrs, dr);

@@ -103,7 +103,12 @@ struct View {
   // batch
   const Node* nodes;
   const ResHeader* hdr;
+  const HotHdr* hot;     // hot header plane (kyv_layout.h), or nullptr: KYV_HOTHDR=0, the kernels read hdr[]
   uint32_t nres;
+  // per-wave facts (kyv_layout.h WaveFacts), one row per match wave; a kernel uses (maps & fact_and): the
+  // KYV_FACT_MAPS switch sets it to 0, "nothing known"
+  const WaveFacts* facts;
+  uint32_t fact_and;
   const FloatAux* faux;
   const uint32_t* str_off;
   const uint32_t* str_len;

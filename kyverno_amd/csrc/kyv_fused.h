@@ -23,13 +23,13 @@ __device__ __forceinline__ void walk_fused(const View& v, DevOut o, uint32_t nwa
   for (uint32_t w = blockIdx.x; w < nwaves; w += gridDim.x) {
     const uint32_t r = w * WAVE + lane;
     const bool active = r < v.nres;
-    uint32_t hflags = 0, hroot = 0, cls = 0;
+    uint32_t hflags = 0, hroot = 0, hnn = 0, cls = 0;
     if (active) {
-      const ResHeader* h = v.hdr + r;
-      hflags = gld32(&h->flags);
-      hroot = gld32(&h->root);
-      cls = gld32(&h->kclass);
-      KYV_ACCT_ADD(0, 12);  // header: flags, root, kind class
+      const HotHdr h = ghot(v, r);  // header: flags, root, node count, kind class
+      hflags = h.flags;
+      hroot = h.root;
+      hnn = h.nnodes;
+      cls = h.kclass;
     }
     // the wave's kind-gate words: one scalar load each when every active lane has the same kind class (kind-major
     // batches: all but the waves at kind boundaries), else per lane
@@ -44,7 +44,7 @@ __device__ __forceinline__ void walk_fused(const View& v, DevOut o, uint32_t nwa
         else if (active) gw[i] = gld32(v.gate + (size_t)cls * v.gate_words + i);
       }
     }
-    f.run(v, o, nwaves, w, r, active, hflags, hroot, gw);
+    f.run(v, o, nwaves, w, r, active, hflags, hroot, hnn, gw);
   }
 }
 
@@ -68,15 +68,16 @@ __device__ __forceinline__ void walk_shapes(const View& v, const ShapeOut& so, S
   for (uint32_t w = blockIdx.x; w < so.nwaves; w += gridDim.x) {
     const uint32_t r = w * WAVE + lane;
     const bool active = r < v.nres;
-    uint32_t hflags = 0, hroot = 0, cls = 0;
+    uint32_t hflags = 0, hroot = 0, hnn = 0, cls = 0;
     if (active) {
-      const ResHeader* h = v.hdr + r;
-      hflags = gld32(&h->flags);
-      hroot = gld32(&h->root);
-      cls = gld32(&h->kclass);
-      KYV_ACCT_ADD(0, 12);  // header: flags, root, kind class
+      const HotHdr h = ghot(v, r);  // header: flags, root, node count, kind class
+      hflags = h.flags;
+      hroot = h.root;
+      hnn = h.nnodes;
+      cls = h.kclass;
     }
-    f.run(v, so, r, active, hflags, hroot, cls);
+    (void)hnn;
+    f.run(v, so, r, active, hflags, hroot, cls, wave_maps(v, w));
   }
 }
 

@@ -142,6 +142,9 @@ struct Ruleset {
   std::vector<uint32_t> pe_self;  // existence entry -> self column of the candidate elements
   std::vector<uint32_t> pn_len;   // array pnode -> its length column (TrieNode::lencol) or NONE
   std::vector<uint32_t> pe_len;   // existence entry -> length column of the candidate array
+  // per-wave facts (compiler.cpp assign_wave_facts): all-maps bit j <-> row space fact_spaces[j]; the flattener
+  // (Batch::facts) and the generated kernels (jit.cpp) number bits by it
+  std::vector<uint32_t> fact_spaces;
   // runtime-compiled walk kernel (jit.cpp): generated once per ruleset, compiled on first use
   bool jit_tried = false;
   std::vector<uint8_t> jit_rules;   // rule k is walked by the compiled kernel
@@ -174,6 +177,7 @@ struct Batch {
   Dict dict;                      // ruleset dict + batch strings
   bulk_vector<Node> nodes;
   bulk_vector<ResHeader> hdr;
+  bulk_vector<HotHdr> hot;        // hot header plane (kyv_layout.h), one row per header, same order
   std::vector<FloatAux> faux;
   std::vector<uint32_t> str_off, str_len, str_flags;
   std::vector<uint32_t> str_upper, str_rx;  // JMESPath functions on the dictionary (empty: the ruleset uses none)
@@ -192,6 +196,8 @@ struct Batch {
   // path columns (kyv_layout.h): colv[col_off[c] + row]
   bulk_vector<uint64_t> colv;
   std::vector<uint32_t> col_off, rs_rows;
+  // per-wave facts (kyv_layout.h WaveFacts), one row per match wave of 64 resources, filled by resolve_path_columns
+  std::vector<WaveFacts> facts;
   std::vector<void*> dev;
   ~Batch();
 };
@@ -233,6 +239,10 @@ Batch* build_batch(const Ruleset* rs, const char* json, size_t len, const char* 
                    std::string* err);
 void derive_strings(Batch& b, size_t from, int threads);
 void build_path_trie(Ruleset& rs);
+void assign_wave_facts(Ruleset& rs);
+// KYV_FACT_MAPS=0: the batch reports "nothing known" (every all-maps bit clear) to the kernels and to
+// kyv_batch_wave_facts; read per evaluation, no recompile
+uint32_t wave_maps_mask();  // AND-ed with a row's all-maps word
 void assign_glob_masks(Ruleset& rs);
 void assign_cond_sets(Ruleset& rs);
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond = nullptr,

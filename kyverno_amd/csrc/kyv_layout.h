@@ -131,6 +131,28 @@ struct ResHeader {          // 64 bytes, one per resource (unstructured accessor
 };
 static_assert(sizeof(ResHeader) == 64, "header size");
 
+// Hot header plane (round 7): the four header words the compiled walk and condition kernels read, one 16-byte row per
+// resource in its own 256-byte-aligned array of the batch image. A wave reads its 64 rows with one 16-byte load per
+// lane (1 KB, eight whole 128-byte lines); the same words out of ResHeader are three dwords at a 64-byte stride,
+// which pulls all 4 KB of the wave's headers through the memory side. The flattener writes it last, after the path
+// columns are resolved (resolve_path_columns sets RF_MAGIC on resources too large for columns). ResHeader stays the
+// record of the match, PodSecurity and interpreted kernels.
+struct HotHdr {
+  uint32_t root, nnodes, flags, kclass;  // = the ResHeader fields of the same names
+};
+static_assert(sizeof(HotHdr) == 16, "hot header row size");
+
+// Per-wave facts (round 7): one row per match wave of 64 resources (resources 64 w .. 64 w + 63 of the kind-major
+// batch), filled by the flattener while it resolves the path columns and read by the compiled kernels with one scalar
+// load per wave. Bit numbering: Ruleset::fact_spaces (compiler.cpp assign_wave_facts).
+//   maps bit j: every element of the wave's lists in row space fact_spaces[j] is a non-null object
+// "Nothing known" is maps = 0: every load is issued as before round 7.
+constexpr uint32_t FACT_BITS = 32;
+struct WaveFacts {
+  uint32_t maps;
+};
+static_assert(sizeof(WaveFacts) == 4, "wave facts row size");
+
 // ---------------------------------------------------------------- match programs
 enum MatchMode : uint8_t { MM_NONE = 0, MM_PLAIN = 1, MM_ANY = 2, MM_ALL = 3,
                            MM_EXC_ALL = 4 };  // a PolicyException match with neither any nor all: matches everything

@@ -75,6 +75,32 @@ constexpr uint32_t T_UNK = 0xE;  // node type not known yet (row not loaded)
 
 __device__ __forceinline__ uint32_t gld32(const uint32_t* p) { return *(const KYV_AS_GLOBAL uint32_t*)p; }
 
+// The header words of resource r (r < v.nres: the caller keeps inactive tail lanes out): one 16-byte load of the
+// resource's hot row, or, without the plane (View::hot == nullptr, a wave-uniform test), the same words out of hdr[]
+__device__ __forceinline__ HotHdr ghot(const View& v, uint32_t r) {
+  HotHdr h;
+  if (v.hot) {
+    const kyv_u32x4 x = *(const KYV_AS_GLOBAL kyv_u32x4*)(v.hot + r);
+    h.root = x.x; h.nnodes = x.y; h.flags = x.z; h.kclass = x.w;
+    KYV_ACCT_ADD(0, 16);  // hot header row
+  } else {
+    const ResHeader* p = v.hdr + r;
+    h.root = gld32(&p->root); h.nnodes = gld32(&p->nnodes); h.flags = gld32(&p->flags); h.kclass = gld32(&p->kclass);
+    KYV_ACCT_ADD(0, 16);  // header: root, node count, flags, kind class
+  }
+  return h;
+}
+// All-maps facts of match wave w (w wave-uniform: one scalar load), the run-time switch applied; without a facts array
+// nothing is known
+__device__ __forceinline__ uint32_t wave_maps(const View& v, uint32_t w) {
+  return v.facts ? (sld32(&v.facts[w].maps) & v.fact_and) : 0u;
+}
+// one header word alone (a compiled map function's metadata-shape flags: jit.cpp)
+__device__ __forceinline__ uint32_t ghot_flags(const View& v, const ResHeader* hp) {
+  KYV_ACCT_ADD(0, 4);
+  return v.hot ? gld32(&v.hot[hp - v.hdr].flags) : gld32(&hp->flags);
+}
+
 // Column entry of one map-entry lookup (the device entry table holds absolute column offsets in `col`)
 __device__ __forceinline__ uint32_t wcol(const View& v, const PEntry& E, bool al, uint32_t row) {
   if (al) KYV_ACCT_ADDK(2u, 0, 4);
@@ -247,6 +273,7 @@ struct WaveWalker {
   UFrame* uf;      // LDS, [cap]
   int cap;
   bool rootmap;    // per lane (unused by the interpreter)
+  uint32_t am = 0u;  // the chunk's all-maps facts (likewise)
 
   __device__ void run(const View& v, uint32_t root, bool walk, const Node* R, const ResHeader* hp, uint32_t row,
                       const RuleDesc& rd, PatOut& out) {
@@ -614,6 +641,7 @@ struct JW {
   uint64_t idx;          // array indices of the failing path
   uint32_t mbase;        // rule's first metadata-expansion site
   uint8_t ost;
+  uint32_t am;           // the wave's all-maps facts (WaveFacts::maps; wave-uniform)
 };
 // one simple comparison with the atom's operator, flags and glob class as template constants (the generated
 // leaf code instantiates exactly the branches watom_simple would take for that atom)
@@ -795,17 +823,15 @@ __device__ __forceinline__ void walk_chunks(const View& v, DevOut o, WorkLists w
       r = w * WAVE + lane;
       bool gated = false;
       if (r < v.nres) {
-        const ResHeader* h = v.hdr + r;
-        const uint32_t fl = gld32(&h->flags);
+        const HotHdr h = ghot(v, r);  // header: flags, root, kind class
+        const uint32_t fl = h.flags;
         if (uniform) {
           gated = true;  // the host checked the wave's (single) kind class against the rule
         } else {
-          const uint32_t cls = gld32(&h->kclass);
-          gated = (gld32(v.gate + (size_t)cls * v.gate_words + (k >> 5)) >> (k & 31)) & 1u;
+          gated = (gld32(v.gate + (size_t)h.kclass * v.gate_words + (k >> 5)) >> (k & 31)) & 1u;
         }
         magic = gated && (fl & RF_MAGIC);  // pattern pairs on such resources go to the CPU engine (pair_dispatch)
-        if (gated) KYV_ACCT_ADD(0, uniform ? 8 : 12);  // header: flags, root (+ kind class)
-        it = make_uint2(r | ((fl & RF_ROOT_MAP) ? ITEM_ROOT_MAP : 0u), gld32(&h->root));
+        it = make_uint2(r | ((fl & RF_ROOT_MAP) ? ITEM_ROOT_MAP : 0u), h.root);
       }
       active = gated && !magic;
       if (!uniform && !__ballot(gated)) continue;
@@ -818,6 +844,7 @@ __device__ __forceinline__ void walk_chunks(const View& v, DevOut o, WorkLists w
       r = it.x & ~ITEM_ROOT_MAP;
     }
     wk.rootmap = (it.x & ITEM_ROOT_MAP) != 0;
+    wk.am = wave_maps(v, w);  // a chunk's resources are those of match wave w
     const uint32_t alts = rd.kind == RK_PATTERN ? 1u : min(rd.nalts, (uint32_t)MAX_ALTS);
     WaveSink sink{o.stage + sld32(o.rbase + (k - o.rule_lo)) + (size_t)w * WAVE * alts, 0u, rd.uses_meta != 0};
     uint8_t st = pair_walk(v, rd, active, r, k, v.nodes + it.y, wk, sink);

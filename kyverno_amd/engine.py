@@ -115,6 +115,24 @@ class Batch:
         K.check(K.lib().kyv_batch_stats_get(self.h, ctypes.byref(s)))
         return {f: getattr(s, f) for f, _ in K.BatchStats._fields_}
 
+    def wave_facts(self):
+        """What the flattener tells the compiled kernels about whole match waves (kyv_batch_wave_facts): a dict of
+        `facts` uint32 [waves] (all-maps bits), `hot` uint32 [n, 4] (root, node count, flags, kind class per
+        resource), `order` uint32 [n] (position in the batch's kind-major order -> input index) and the bits'
+        meaning, `maps`: one path (list of segments) per bit"""
+        L = K.lib()
+        o = K.WaveFactsOut()
+        K.check(L.kyv_batch_wave_facts(self.h, ctypes.byref(o)))
+        nw = (self.n + 63) // 64
+        facts = np.zeros(nw, dtype=np.uint32)
+        hot = np.zeros((self.n, 4), dtype=np.uint32)
+        order = np.zeros(self.n, dtype=np.uint32)
+        bits = ctypes.create_string_buffer(o.bits_len + 1)
+        o = K.WaveFactsOut(facts.ctypes.data, facts.size, hot.ctypes.data, hot.size, order.ctypes.data, order.size,
+                           ctypes.addressof(bits), o.bits_len + 1, 0)
+        K.check(L.kyv_batch_wave_facts(self.h, ctypes.byref(o)))
+        return dict(json.loads(bits.value.decode()), facts=facts, hot=hot, order=order)
+
     def __del__(self):
         if getattr(self, "h", None):
             K.lib().kyv_batch_free(self.h)
