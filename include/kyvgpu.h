@@ -198,6 +198,11 @@ typedef struct kyv_wave_facts_out {
 } kyv_wave_facts_out;
 int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out);
 
+/* The batch builder's size guard, as it decides it: 1 when a path-column table of `entries` 8-byte entries (all
+ * columns' rows together) can be built, 0 when kyv_batch_build refuses the batch ("split the batch"). Column offsets
+ * are 32-bit words and the compiled kernels add offset + row in 32 bits, so the limit lies just under 2^32. */
+int kyv_col_entries_fit32(uint64_t entries);
+
 /* ---- evaluation: engine.Validate over every (resource, rule) pair ---- */
 int kyv_eval(const kyv_ruleset* rs, const kyv_batch* b, const kyv_eval_opts* opts, kyv_results** out);
 void kyv_results_free(kyv_results* r);

@@ -1275,7 +1275,7 @@ void resolve_path_columns(Batch& b, int threads) {
   std::vector<uint64_t> tot(nsp, 0);
   for (size_t c = 0; c < nch; c++)
     for (uint32_t s = 1; s < nsp; s++) {
-      if (tot[s] + cnt[c][s] > 0xFFFFFFF0ull) throw std::runtime_error("path-column row space exceeds 2^32 rows; split the batch");
+      if (!col_entries_fit32(tot[s] + cnt[c][s])) throw std::runtime_error("path-column row space exceeds 2^32 rows; split the batch");
       base[c][s] = (uint32_t)tot[s];
       tot[s] += cnt[c][s];
     }
@@ -1285,7 +1285,7 @@ void resolve_path_columns(Batch& b, int threads) {
   for (uint32_t c = 0; c < rs.ncols; c++) {
     b.col_off[c] = (uint32_t)total;
     total += b.rs_rows[rs.col_rowspace[c]];
-    if (total > 0xFFFFFFF0ull) throw std::runtime_error("path columns exceed 2^32 entries; split the batch");
+    if (!col_entries_fit32(total)) throw std::runtime_error("path columns exceed 2^32 entries; split the batch");
   }
   b.colv.resize(total + 1);  // NONE-initialised in parallel, one slice per worker
   {

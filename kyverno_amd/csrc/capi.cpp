@@ -84,6 +84,7 @@ extern "C" {
 
 const char* kyv_last_error(void) { return g_err.c_str(); }
 const char* kyv_version(void) { return "kyvgpu 0.1 (gfx950)"; }
+int kyv_col_entries_fit32(uint64_t entries) { return kyv::col_entries_fit32(entries) ? 1 : 0; }
 
 int kyv_ruleset_compile(const char* json, size_t len, const kyv_compile_opts* opts, kyv_ruleset** out) {
   return kyv_ruleset_compile_ex(json, len, nullptr, 0, opts, out);

@@ -50,6 +50,8 @@ struct Gen {
   // array-of-maps elements whose column loads are issued together (KYV_JIT_BATCH; default 1 = one element at a
   // time: batches of 2 / 4 measured 2.1x slower on C3, 1.41 -> 2.97 ms walk, registers past the 4-wave budget)
   const size_t batch_max = getenv("KYV_JIT_BATCH") ? (size_t)std::max(1, atoi(getenv("KYV_JIT_BATCH"))) : 1;
+  // leaf functions with a wave-uniform fast path for typed / absent values (node(), P_LEAF); KYV_JIT_LEAF_FAST=0: off
+  const bool leaf_fast = !getenv("KYV_JIT_LEAF_FAST") || atoi(getenv("KYV_JIT_LEAF_FAST")) != 0;
 
   // Column scopes: the pattern root and every array-element pattern open a scope (one row of one row space);
   // every column lookup of the maps inside a scope (not crossing into array elements) is loaded up front by
@@ -259,8 +261,18 @@ struct Gen {
       case P_LEAF:
         // a string / boolean / null whose type and `a` came with the column needs no row read
         out << "  const bool known = rt == N_STR || rt == N_TRUE || rt == N_FALSE || rt == N_NULL;\n"
-               "  Node n{0u, 0u, 0u, 0u};\n  if (rn != NONE && !known) n = gnode(w.R + rn);\n";
-        out << "  bool fb = false, okv = true;\n";
+               "  bool fb = false, okv = true;\n";
+        // the common wave: every lane's value is absent or came typed with its column entry. One wave-uniform test
+        // takes such a wave through a straight-line compare (no node row, no array-valued-leaf loop); a wave with a
+        // number, a map or an array at this leaf in some lane runs the general form below for all its lanes, as before
+        if (leaf_fast)
+          out << "  if (__ballot(rn != NONE && !known) == 0ull) {\n"
+                 "    const Val x = jvalue_typed(rn, rt, ra);\n"
+                 "    " << leaf_code(P.first) << "\n"
+                 "    if (fb) { w.ost = ST_FALLBACK; return ok_ret(); }\n"
+                 "    return okv ? ok_ret() : mkerr(EC_NONE, 0, " << T << ");\n"
+                 "  }\n";
+        out << "  Node n{0u, 0u, 0u, 0u};\n  if (rn != NONE && !known) n = gnode(w.R + rn);\n";
         out << "  const bool each = rn != NONE && !known && node_type(n) == N_ARR;\n"
                "  const uint32_t cnt = each ? n.b : 1u;\n"
                "  for (uint32_t i = 0; i < cnt && okv; i++) {\n"
@@ -1465,6 +1477,18 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   // 368): C3 walk 6.86 -> 10.67 ms, conditions 2.53 -> 3.95 ms. Default: the plain reference.
   src << "__device__ __forceinline__ const View* kyv_launder(const View* p) { asm volatile(\"\" : \"+s\"(p)); return p; }\n"
          "#ifndef KYV_RULE_VIEW\n#define KYV_RULE_VIEW(x) (x)\n#endif\n";
+  // jvalue (kyv_wave.h) for a lane whose value is absent (idx NONE) or typed by its column entry (string, boolean,
+  // null): no row read, no call into the node decoder (the leaf functions' wave-uniform fast path, Gen::node)
+  src << "__device__ __forceinline__ Val jvalue_typed(uint32_t idx, uint32_t t, uint32_t a) {\n"
+         "  if (idx == NONE) return wvalue_absent();\n"
+         "  Val x;\n"
+         "  x.t = t; x.wsid = NONE; x.nsid = NONE; x.sid = NONE; x.i = 0; x.f = 0;\n"
+         "  if (t == N_STR) { x.sid = a; x.wsid = a; x.nsid = a; }\n"
+         "  else if (t == N_TRUE) x.wsid = SID_TRUE;\n"
+         "  else if (t == N_FALSE) x.wsid = SID_FALSE;\n"
+         "  else x.nsid = SID_ZERO;\n"
+         "  return x;\n"
+         "}\n";
   src << body.str();
   if (!crules.empty()) {
     // the match part of pair_dispatch, out of line (one copy for every rule that needs more than the kind gate):
@@ -1932,6 +1956,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     // kind read the same container lists) in the caches. KYV_JC_GROUP=0: one kernel per rule (kyv_jit_cond_<k>)
     // 5 waves/SIMD: measured 1.30 -> 1.05 ms on C3 with the round-2 kernel (4: 1.11, 6: 1.08); round 6 (12 rules in 3
     // kernels, C3 10M, condition phase ms): 5 (77 VGPRs) 3.05, 6 3.07, 7 2.88, 8 (64 VGPRs, 74 spills) 2.82
+    // (round 8: 7 measured slower again, see KYV_JIT_WPE_FUSED below)
     src << "#ifndef KYV_JC_WPE\n#define KYV_JC_WPE 8\n#endif\n";
     const bool grouped = !getenv("KYV_JC_GROUP") || atoi(getenv("KYV_JC_GROUP")) != 0;
     const std::string& lds = jc_lds;
@@ -1990,6 +2015,9 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   // VGPR spills, 5 GB of scratch writes per evaluation; one kernel, C3 walk ms: 8 waves 9.44, 7: 8.14, 6: 8.11,
   // 5: 8.46, 4: 9.53); split in parts (KYV_FUSED_SPLIT, above) each part fits 8 waves with a few spills
   // (the group of wildcard-metadata rules keeps the walk's heavy target, KYV_JIT_WPE_FUSED_HEAVY = 4)
+  // Round 8 measured 7 waves/SIMD (94 SGPRs, 72 VGPRs) for the fused parts and the condition kernels again: a third
+  // to two thirds fewer SGPR spills and no VGPR spill (profiles/r8/isa_c3_w7.txt), but 0.4 ms per C3 step slower than 8
+  // (DESIGN section 4, round 8), as round 6 found: the kernels need the eighth wave more than the registers.
   src << "#ifndef KYV_JIT_WPE_FUSED\n#define KYV_JIT_WPE_FUSED 8\n#endif\n"
          "#ifndef KYV_JIT_WPE_FUSED_HEAVY\n#define KYV_JIT_WPE_FUSED_HEAVY 4\n#endif\n";
   for (const auto& gp : fused_kernels) {

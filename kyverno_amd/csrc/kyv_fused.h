@@ -20,7 +20,16 @@ namespace kyv {
 template <class Fused>
 __device__ __forceinline__ void walk_fused(const View& v, DevOut o, uint32_t nwaves, Fused& f) {
   const uint32_t lane = threadIdx.x & (WAVE - 1);
+  // One wave per match wave: the launch grid is nwaves (kyv_engine.hip), so this is no grid-stride loop. As a loop
+  // (round 4-7) every rule's wave-uniform values that do not depend on the match wave -- its slice test, its rbase /
+  // rcnt / status addresses -- were hoisted in front of it, held in SGPRs through every rule of the part and so
+  // spilled to VGPR lanes and read back (v_readlane) at their rule: C3 kyv_jit_fused_0 188 of its 1,313 SGPR spills
+  // in the kernel prologue. KYV_FUSED_STRIDE restores the loop (experiments).
+#ifdef KYV_FUSED_STRIDE
   for (uint32_t w = blockIdx.x; w < nwaves; w += gridDim.x) {
+#else
+  if (const uint32_t w = blockIdx.x; w < nwaves) {
+#endif
     const uint32_t r = w * WAVE + lane;
     const bool active = r < v.nres;
     uint32_t hflags = 0, hroot = 0, hnn = 0, cls = 0;

@@ -26,7 +26,7 @@ __device__ __forceinline__ uint64_t jc_col(const View& v, uint32_t col, uint32_t
   if (row == NONE) return COL_NONE;
   KYV_ACCT_ADDK(2u, 0, 8);
   const uint32_t off = sld32(v.col_off + col);
-  return *(const KYV_AS_GLOBAL uint64_t*)(v.colv + (size_t)off + row);
+  return gcol(v.colv, off, row);
 }
 __device__ __forceinline__ uint32_t jc_dec(uint64_t x, uint32_t* t, uint32_t* a) {
   const uint32_t lo = (uint32_t)x;

@@ -240,6 +240,12 @@ struct PEntry {         // 20 bytes
 // batch-wide, with a "self" column holding each element; an array node's `c` holds the row of its element 0.
 constexpr uint32_t COL_TYPE_SHIFT = 28;
 constexpr uint32_t COL_INDEX_MASK = (1u << COL_TYPE_SHIFT) - 1;
+// The guard of the 32-bit column addressing: a batch is built only while its column table (all columns' rows
+// together) stays under 2^32 entries, with a margin of 16 for NONE and the table's sentinel entry. Column offsets
+// are 32-bit words, and the compiled kernels add offset + row in 32 bits (kyv_wave.h gcol); a larger batch is refused
+// at batch build (batch.cpp resolve_path_columns: "split the batch").
+constexpr uint64_t COL_ENTRIES_MAX = 0xFFFFFFF0ull;
+constexpr bool col_entries_fit32(uint64_t entries) { return entries <= COL_ENTRIES_MAX; }
 
 // L_DYN: a foreach pattern value that is exactly one element variable ({{element...}} / {{elementIndex}}); `exact`
 // holds its slot in the entry's dynamic-value list, resolved per element before the walk (vars.go:352-431 substitutes

@@ -667,18 +667,30 @@ __device__ __forceinline__ bool jatom(const View& v, const Val& x, uint32_t pat,
   return false;
 }
 constexpr uint64_t COL_NONE = 0xFFFFFFFFull;
+// 8-byte entry `row` of the path column at absolute offset `off` (wave-uniform) of colv. The sum off + row is taken in
+// 32 bits: a batch whose column table holds 2^32 entries or more is refused when it is built (col_entries_fit32,
+// kyv_layout.h; batch.cpp resolve_path_columns), so the sum cannot wrap. The only 64-bit value the address needs is
+// then colv itself; written as colv + (size_t)off + row (round 2-7, -DKYV_COL64) every column gets a 64-bit base of
+// its own (s_lshl_b64 / s_add_u32 / s_addc_u32 on the offset), an SGPR pair the compiler computes early and keeps.
+__device__ __forceinline__ uint64_t gcol(const uint64_t* colv, uint32_t off, uint32_t row) {
+#ifdef KYV_COL64
+  return *(const KYV_AS_GLOBAL uint64_t*)(colv + (size_t)off + row);
+#else
+  return *(const KYV_AS_GLOBAL uint64_t*)(colv + (uint32_t)(off + row));
+#endif
+}
 // raw 8-byte column entry of a lookup (speculative preload of a column scope; NONE rows give COL_NONE); the
 // device entry table holds the column's absolute offset in `col`
 __device__ __forceinline__ uint64_t jraw(const JW& w, uint32_t e, uint32_t row) {
   const uint32_t off = sld32(&w.v.pe[e].col);
   if (row != NONE) KYV_ACCT_ADDK(4u, 0, 8);
-  return row == NONE ? COL_NONE : *(const KYV_AS_GLOBAL uint64_t*)(w.v.colv + (size_t)off + row);
+  return row == NONE ? COL_NONE : gcol(w.v.colv, off, row);
 }
 // self column (array elements) by column id
 __device__ __forceinline__ uint64_t jself(const JW& w, uint32_t col, uint32_t row) {
   const uint32_t off = sld32(w.v.col_off + col);
   if (row != NONE) KYV_ACCT_ADDK(8u, 0, 8);
-  return row == NONE ? COL_NONE : *(const KYV_AS_GLOBAL uint64_t*)(w.v.colv + (size_t)off + row);
+  return row == NONE ? COL_NONE : gcol(w.v.colv, off, row);
 }
 // entry -> node index (NONE absent), type (T_UNK absent) and the node's `a`
 __device__ __forceinline__ uint32_t jdec(uint64_t x, uint32_t* t, uint32_t* a) {
