@@ -225,6 +225,30 @@ int kyv_results_phase_ms(const kyv_results* r, double* out, size_t cap);
  * runtime-compiled condition kernel evaluated its deny / foreach rules with JMESPath operands; bit 2: pattern-shape
  * tables (each distinct compiled pattern walked once per resource) decided the matched pairs of record rules */
 int kyv_results_jit(const kyv_results* r);
+/* The configuration an evaluation ran in (diagnostics, read-only; not a reference interface): which of the device
+ * code's capacity-dependent paths a ruleset and batch reached, so a parity test can prove the regime it claims.
+ * From the ruleset alone (either backend): gmask_patterns wildcard / non-ASCII literals with a glob-mask bit, cond_sets
+ * condition literal sets with one, gmask_words mask words per dictionary string (GPU: the count the kernels were
+ * chosen by, 0 with masks switched off), unmasked_literals wildcard / non-ASCII ruleset literals left without a bit
+ * (they match bytes). From a GPU evaluation (zero on the CPU backend): onemask (the lane tail facts read mask word 0
+ * only); per lane tail table -- [0] selector keys, [1] namespace-selector keys, [2] wildcard requirements,
+ * [3] annotation pairs, [4] group / version atoms -- tail_used entries filled and tail_candidates distinct candidates
+ * seen (candidates > used: the table overflowed); fast_records / fasteval_records rules evaluated as staged match
+ * records / of those on the branch-free path; generic_rules rules on the generic match kernel; slices rule slices.
+ * kyv_results_plan_slices: per slice its rule range [k0, k1) and the rules in it walked by fused kernels, by chunk
+ * kernels and evaluated by compiled condition kernels; returns the slice count (copies min(count, cap)). */
+typedef struct {
+  uint32_t gmask_patterns, cond_sets, gmask_words, unmasked_literals;
+  uint32_t onemask;
+  uint32_t tail_used[5], tail_candidates[5];
+  uint32_t fast_records, fasteval_records, generic_rules;
+  uint32_t slices;
+} kyv_eval_plan;
+typedef struct {
+  uint32_t k0, k1, fused_rules, chunk_rules, cond_rules;
+} kyv_slice_plan;
+int kyv_results_plan(const kyv_results* r, kyv_eval_plan* out);
+int64_t kyv_results_plan_slices(const kyv_results* r, kyv_slice_plan* out, size_t cap);
 /* with KYV_EVAL_ACCOUNT_BYTES: algorithmic bytes of the evaluation (GPU: counted by the accounting build of the
  * kernels -- node rows, path-column entries, header fields, work lists read; verdicts, PSS masks, failing-path records,
  * work lists written; CPU: header fields, distinct node rows, verdict, PSS mask, failure records per pair); 0 otherwise */

@@ -65,7 +65,8 @@ EXPORTS = [
     "kyv_results_texts", "kyv_results_phase_ms", "kyv_results_alg_bytes_phase", "kyv_results_alg_bytes_class", "kyv_batch_export_status", "kyv_batch_copy_status",
     "kyv_batch_export_failures", "kyv_comm_unique_id", "kyv_comm_init", "kyv_comm_free", "kyv_comm_gather_results",
     "kyv_comm_gathered_status", "kyv_comm_gathered_failures", "kyv_comm_gather_report", "kyv_comm_reduce_counts", "kyv_results_batch_ms",
-    "kyv_calibrate_fetch", "kyv_batch_wave_facts", "kyv_col_entries_fit32",
+    "kyv_calibrate_fetch", "kyv_batch_wave_facts", "kyv_col_entries_fit32", "kyv_results_plan",
+    "kyv_results_plan_slices",
 ]
 
 
@@ -73,6 +74,19 @@ class WaveFactsOut(ctypes.Structure):
     _fields_ = [("facts", ctypes.c_void_p), ("facts_cap", ctypes.c_size_t), ("hot", ctypes.c_void_p),
                 ("hot_cap", ctypes.c_size_t), ("order", ctypes.c_void_p), ("order_cap", ctypes.c_size_t),
                 ("bits", ctypes.c_void_p), ("bits_cap", ctypes.c_size_t), ("bits_len", ctypes.c_size_t)]
+
+
+class EvalPlan(ctypes.Structure):
+    _fields_ = [("gmask_patterns", ctypes.c_uint32), ("cond_sets", ctypes.c_uint32), ("gmask_words", ctypes.c_uint32),
+                ("unmasked_literals", ctypes.c_uint32), ("onemask", ctypes.c_uint32),
+                ("tail_used", ctypes.c_uint32 * 5), ("tail_candidates", ctypes.c_uint32 * 5),
+                ("fast_records", ctypes.c_uint32), ("fasteval_records", ctypes.c_uint32),
+                ("generic_rules", ctypes.c_uint32), ("slices", ctypes.c_uint32)]
+
+
+class SlicePlan(ctypes.Structure):
+    _fields_ = [("k0", ctypes.c_uint32), ("k1", ctypes.c_uint32), ("fused_rules", ctypes.c_uint32),
+                ("chunk_rules", ctypes.c_uint32), ("cond_rules", ctypes.c_uint32)]
 
 
 class GatherStats(ctypes.Structure):
@@ -161,6 +175,9 @@ def lib():
     L.kyv_calibrate_fetch.restype = ctypes.c_double
     L.kyv_col_entries_fit32.argtypes = [ctypes.c_uint64]
     L.kyv_col_entries_fit32.restype = i32
+    L.kyv_results_plan.argtypes = [vp, ctypes.POINTER(EvalPlan)]
+    L.kyv_results_plan_slices.argtypes = [vp, ctypes.c_void_p, sz]
+    L.kyv_results_plan_slices.restype = i64
     L.kyv_results_alg_bytes.argtypes = [vp]
     L.kyv_results_alg_bytes.restype = ctypes.c_uint64
     L.kyv_results_message.argtypes = [vp, vp, vp, u32, u32, ctypes.c_char_p, sz]

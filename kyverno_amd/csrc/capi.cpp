@@ -410,6 +410,33 @@ int kyv_results_phase_ms(const kyv_results* r, double* out, size_t cap) {
   return 5;
 }
 
+int kyv_results_plan(const kyv_results* r, kyv_eval_plan* out) {
+  if (!r || !out) return fail(KYV_EINVAL, "null argument");
+  const EvalPlan& p = r->r.plan;
+  memset(out, 0, sizeof *out);
+  out->gmask_patterns = p.gmask_patterns;
+  out->cond_sets = p.cond_sets;
+  out->gmask_words = p.gmask_words;
+  out->unmasked_literals = p.unmasked;
+  out->onemask = p.onemask;
+  for (int q = 0; q < 5; q++) { out->tail_used[q] = p.tail_used[q]; out->tail_candidates[q] = p.tail_cand[q]; }
+  out->fast_records = p.fast;
+  out->fasteval_records = p.fasteval;
+  out->generic_rules = p.generic;
+  out->slices = (uint32_t)r->r.slices.size();
+  return KYV_OK;
+}
+
+int64_t kyv_results_plan_slices(const kyv_results* r, kyv_slice_plan* out, size_t cap) {
+  if (!r) return fail(KYV_EINVAL, "null argument"), -1;
+  const size_t n = r->r.slices.size();
+  for (size_t i = 0; i < n && out && i < cap; i++) {
+    const SlicePlan& s = r->r.slices[i];
+    out[i] = kyv_slice_plan{s.k0, s.k1, s.fused, s.chunk, s.cond};
+  }
+  return (int64_t)n;
+}
+
 uint64_t kyv_results_alg_bytes(const kyv_results* r) { return r ? r->r.alg_bytes : 0; }
 
 int kyv_results_alg_bytes_class(const kyv_results* r, uint64_t* out, size_t cap) {

@@ -2603,6 +2603,22 @@ void assign_glob_masks(Ruleset& rs) {
   assign_cond_sets(rs);
 }
 
+// The ruleset side of an evaluation's plan report (kyvgpu.h kyv_eval_plan): what assign_glob_masks decided
+void plan_ruleset(const Ruleset& rs, EvalPlan* p) {
+  p->gmask_patterns = (uint32_t)rs.gpats.size();
+  p->cond_sets = (uint32_t)rs.gsets.size();
+  p->gmask_words = (uint32_t)((rs.gpats.size() + rs.gsets.size() + 31) / 32);
+  std::vector<uint8_t> masked(rs.dict.strs.size(), 0);
+  for (uint32_t s : rs.gpats) if (s < masked.size()) masked[s] = 1;
+  p->unmasked = 0;
+  for (uint32_t s = 0; s < rs.dict.strs.size(); s++) {
+    const std::string& x = rs.dict.strs[s];
+    bool globby = x.find_first_of("*?") != std::string::npos;
+    for (unsigned char ch : x) if (ch >= 0x80) globby = true;
+    if (globby && !masked[s]) p->unmasked++;
+  }
+}
+
 // Condition-set masks: an AnyIn / AllIn / AnyNotIn / AllNotIn (or In / NotIn with a scalar key) condition with one
 // literal side and one JMESPath side asks, per element of the resource-side list, "does wild2(element, e) hold for
 // some literal element e" (op_any_all / key_exists, kyv_cond.h; anyin.go:115-180, in.go:52-86). That predicate depends

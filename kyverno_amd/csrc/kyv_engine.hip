@@ -22,6 +22,7 @@
 #include <functional>
 #include <cstdlib>
 #include <mutex>
+#include <set>
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -379,6 +380,8 @@ struct SliceSched {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // after match, condition, walk, compaction (phase timing)
   hipEvent_t cev[2] = {nullptr, nullptr};  // the slice's condition kernels on the condition stream (start, end)
   int jit_state = -1;            // what the schedules were laid out for (0 interpreter only, 1 with the jit kernel)
+  SlicePlan plan;                // what layout_schedule decided, for the plan report (kyv_results_plan_slices)
+  uint32_t nfe = 0;              // records of mrec on the branch-free path (MR_FASTEVAL)
 };
 
 struct DeviceResults {
@@ -428,6 +431,8 @@ struct DeviceResults {
   TailCfg* tcfg = nullptr;
   ResFacts* facts = nullptr;
   bool facts_on = false;
+  EvalPlan plan;                 // the tail tables of tcfg: entries used and candidates seen (kyv_results_plan)
+  bool plan_ruleset_done = false;  // plan's ruleset side (plan_ruleset) is filled in
   WorkLists wl{};                // walk work lists (kyv_wave.h), slice-local rule index
   std::vector<SliceSched> slices;
   int cus = 256;
@@ -1216,7 +1221,8 @@ static void setup_shapes(const Ruleset& rs, const Batch& b, DeviceResults& d, bo
 // each table filled by frequency of use; a tail filter all of whose parts are covered gets a TailProg (MRecFilter.pad
 // = 1 + its index) and is decided from the lane's facts, the others run cb_tail
 static void build_tails(const Ruleset& rs, const std::vector<MRec>& all, std::vector<MRec>& recs,
-                        const std::vector<uint32_t>& gidx, bool onemask, TailCfg& cfg, std::vector<TailProg>& progs) {
+                        const std::vector<uint32_t>& gidx, bool onemask, TailCfg& cfg, std::vector<TailProg>& progs,
+                        uint32_t cand[5]) {
   memset(&cfg, 0, sizeof cfg);
   progs.clear();
   using Wild = std::array<uint32_t, 4>;
@@ -1271,6 +1277,8 @@ static void build_tails(const Ruleset& rs, const std::vector<MRec>& all, std::ve
   cfg.nnsslot = (uint32_t)nsslots.size();
   cfg.nwild = (uint32_t)wilds.size();
   cfg.nann = (uint32_t)anns.size();
+  cand[0] = (uint32_t)keyf.size(); cand[1] = (uint32_t)nskeyf.size(); cand[2] = (uint32_t)wildf.size();
+  cand[3] = (uint32_t)annf.size();
   for (auto& x : slots) cfg.slot[x.second] = x.first;
   for (auto& x : nsslots) cfg.nsslot[x.second] = x.first;
   for (auto& x : wilds) {
@@ -1294,6 +1302,7 @@ static void build_tails(const Ruleset& rs, const std::vector<MRec>& all, std::ve
   // kinds with a group / version refinement: atoms (mode, g, v); the record kind becomes sid | (atom + 1) << 24 and
   // its group / version bit stays set (filt_fast reads the atom, cb_rec / kinds_match the filter)
   std::map<std::array<uint32_t, 3>, uint32_t> gvs;
+  std::set<std::array<uint32_t, 3>> gvseen;
   for (const auto& R : all) {  // the refinement atoms, in ruleset order
     const uint32_t nf = ((R.bits >> 24) & 0xFu) + (R.bits >> 28);
     for (uint32_t j = 0; j < nf && j < MREC_F; j++) {
@@ -1304,6 +1313,7 @@ static void build_tails(const Ruleset& rs, const std::vector<MRec>& all, std::ve
         if (!((F.bits >> (24 + i)) & 1u)) continue;
         const KindDesc& kd = rs.kinds[f.kinds + i];
         const std::array<uint32_t, 3> key{kd.gv_mode, kd.g, kd.v};
+        gvseen.insert(key);
         if (gvs.count(key) || gvs.size() >= TF_GV) continue;
         const uint32_t a = (uint32_t)gvs.size();
         gvs.emplace(key, a);
@@ -1336,6 +1346,7 @@ static void build_tails(const Ruleset& rs, const std::vector<MRec>& all, std::ve
     }
   }
   cfg.ngv = (uint32_t)gvs.size();
+  cand[4] = (uint32_t)gvseen.size();
   std::map<std::string, uint32_t> seen;  // program bytes -> its index
   tails([&](MRecFilter& F) {
     const Filter& f = rs.filters[F.idx];
@@ -1417,6 +1428,7 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
       else if (k < rs.jit_cond.size() && rs.jit_cond[k] >= 2 && dr->ffns[rs.jit_cond[k] - 2])
         sl.fg[rs.jit_cond[k] - 2] = 1;  // a condition rule folded into that group's fused walk (jit.cpp)
   std::vector<std::vector<uint2>> slots(ncls);
+  std::set<uint32_t> chunked;  // rules with walk chunks in some run (plan report)
   for (size_t ri = 0; ri < runs.size(); ri++) {
     const uint32_t wb = runs[ri].first, we = ri + 1 < runs.size() ? runs[ri + 1].first : nw;
     std::vector<std::vector<uint32_t>> ks(ncls);
@@ -1426,6 +1438,7 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
       if (by_shape[k - sl.k0]) continue;  // decided in the match phase from its shape's tables
       if (!((runs[ri].second[k / 32] >> (k % 32)) & 1u)) continue;
       ks[jit ? rs.jit_rules[k] : 0].push_back(k);
+      chunked.insert(k);
     }
     for (uint32_t cls = 0; cls < ncls; cls++)
       for (size_t i = 0; i < ks[cls].size(); i += WIN) {
@@ -1589,6 +1602,7 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
       }
       mw.swap(gen);
       sl.nmr = (uint32_t)recs.size();
+      sl.nfe = 0;
       {  // lane tail facts: one device block [TailCfg][TailProg...]
         TailCfg cfg;
         std::vector<TailProg> progs;
@@ -1607,9 +1621,12 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
             if (R.bits & MR_FAST) all.push_back(R);
           }
           const bool onemask = mrec_masks_on() && rs.gpats.size() + rs.gsets.size() <= 32;
-          build_tails(rs, all, recs, gidx, onemask, cfg, progs);
+          build_tails(rs, all, recs, gidx, onemask, cfg, progs, d.plan.tail_cand);
         }
         else memset(&cfg, 0, sizeof cfg);
+        d.plan.onemask = cfg.onemask;
+        d.plan.tail_used[0] = cfg.nslot; d.plan.tail_used[1] = cfg.nnsslot; d.plan.tail_used[2] = cfg.nwild;
+        d.plan.tail_used[3] = cfg.nann; d.plan.tail_used[4] = cfg.ngv;
         const size_t bytes = sizeof(TailCfg) + std::max<size_t>(1, progs.size()) * sizeof(TailProg);
         dfree(sl.tails);
         sl.tails = nullptr;
@@ -1633,6 +1650,7 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
             if ((F.bits & FF_HAS_NSSEL) && (F.bits & FF_KINDS_STAR)) nsstar = true;
           }
           if (fast) R.bits |= MR_FASTEVAL;
+          if (fast) sl.nfe++;
           if ((R.bits & MR_EMPTY) && !nsstar) {
             bool nd = false;
             const bool em = match_rule(hv, rs.rules[R.k], ResView{NodeTab{nullptr}, nullptr},
@@ -1726,6 +1744,10 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
     at += slots[cls].size();
   }
   sl.jit_state = (int)jit;
+  sl.plan = SlicePlan{sl.k0, sl.k1, 0, (uint32_t)chunked.size(), sl.nmc};
+  if (jit)
+    for (uint32_t k = sl.k0; k < sl.k1; k++)
+      if (rs.jit_rules[k] && jit_rule_fused(rs, k) && dr->ffns[rs.jit_rules[k] - 1]) sl.plan.fused++;
 }
 
 // accumulate one slice's phase times (ms) from its events; `start`: the evaluation's start event for the first slice
@@ -2204,6 +2226,19 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     out->jit_used = (jit ? 1 : 0) | (jit && cond ? 2 : 0) | (jit && d.nshapes ? 4 : 0);
     out->h2d_ms = db->upload_ms;
     out->gmask_ms = db->gmask_ms;
+    if (!d.plan_ruleset_done) {  // a walk over the ruleset dictionary: once per batch, not per evaluation
+      plan_ruleset(rs, &d.plan);
+      d.plan_ruleset_done = true;
+    }
+    out->plan = d.plan;
+    out->plan.gmask_words = v.gmask_words;  // what the kernels were chosen by (0: masks off, strings match bytes)
+    out->slices.clear();
+    for (auto& sl : d.slices) {
+      out->slices.push_back(sl.plan);
+      out->plan.fast += sl.nmr;
+      out->plan.fasteval += sl.nfe;
+      out->plan.generic += sl.nmw;
+    }
     if (acct) {
       out->alg_bytes = 0;
       for (int q = 0; q < 5; q++) { out->alg_bytes_phase[q] = aphase[q]; out->alg_bytes += aphase[q]; }
@@ -2262,6 +2297,7 @@ void eval_cpu(const Ruleset& rs, const Batch& b, int threads, Results* out, bool
   size_t nres = b.hdr.size(), nrules = rs.rules.size();
   out->nres = (uint32_t)nres;
   out->nrules = (uint32_t)nrules;
+  plan_ruleset(rs, &out->plan);
   out->status.assign(nres * nrules, ST_NONE);
   std::vector<uint32_t> pss_slot(nrules, NONE);
   uint32_t npss = 0;

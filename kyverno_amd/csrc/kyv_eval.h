@@ -438,7 +438,11 @@ KYV_HD uint32_t ls_find(const LabelSet& s, uint32_t key) {
   return NONE;
 }
 
-// CheckSelector incl. ReplaceInSelector (pkg/utils/match/labels.go:10-24, wildcards.go:13-50): 1 match, 0 no, -1 error
+// CheckSelector incl. ReplaceInSelector (pkg/utils/match/labels.go:10-24, wildcards.go:13-50): 1 match, 0 no, -1 error.
+// expandWildcards takes the first label, in Go map order, that a wildcard entry matches: with a valid and an invalid
+// hit the selector is the valid choice's outcome on one order and an error on the other. *nd is raised when that
+// changes whether the selector matches (the valid choice matches); a mismatch and an error both leave the block
+// unmatched.
 #ifdef KYV_SEL_INLINE
 KYV_HD __attribute__((always_inline))
 #else
@@ -447,6 +451,7 @@ KYV_BIG
 int check_selector(const View& v, const SelDesc& sd, const LabelSet& ls, bool* nd) {
   if (sd.invalid) return -1;
   int res = 1;
+  bool flip = false;
   for (uint32_t q = 0; q < sd.nreqs; q++) {
     const SelReq& r = v.reqs[sd.reqs + q];
     if (r.op == RQ_WILD) {
@@ -461,7 +466,7 @@ int check_selector(const View& v, const SelDesc& sd, const LabelSet& ls, bool* n
           if (ok) valid_hit = true; else invalid_hit = true;
         }
       }
-      if (nhit > 1 && valid_hit && invalid_hit) *nd = true;
+      if (nhit > 1 && valid_hit && invalid_hit) flip = true;
       if (nhit == 0) {
         if (r.rkey == NONE) return -1;           // replacement key/value invalid -> selector error
         if (ls_find(ls, r.rkey) != NONE && ls_val(ls, ls_find(ls, r.rkey)) == r.rval) {} else res = 0;
@@ -486,6 +491,7 @@ int check_selector(const View& v, const SelDesc& sd, const LabelSet& ls, bool* n
     }
     if (!ok) res = 0;
   }
+  if (flip && res == 1) *nd = true;
   return res;
 }
 
@@ -575,21 +581,33 @@ KYV_FN_MATCH bool match_rule(const View& v, const RuleDesc& rd, const ResView& r
     failed = true;  // MM_NONE never produced by the compiler
   }
   if (failed) return false;
+  // An exclude filter that excludes with its nondeterminism flag raised excludes on one map order only (its selector
+  // errors on the other): the pair is then matched on some order and excluded on another unless the block excludes
+  // without such a filter. It is reported as matched with *nd raised (the callers turn that into ST_ND), so the flag
+  // is not lost with the response.
   const MatchBlock& e = rd.exclude;
+  bool pend = false;
   if (e.mode == MM_ANY || e.mode == MM_PLAIN) {
     for (uint32_t i = 0; i < e.nfilters; i++) {
       const Filter& f = v.filters[e.filters + i];
       if ((f.flags & FF_ZERO_RD) && !(f.flags & FF_USERINFO)) continue;
-      if (condition_block(v, f, rv, nsl, true, nd)) return false;
+      bool fnd = false;
+      const bool c = condition_block(v, f, rv, nsl, true, &fnd);
+      *nd = *nd | fnd;
+      if (c && !fnd) return false;
+      if (c) pend = true;
     }
   } else if (e.mode == MM_ALL) {
     bool byAll = true;
     for (uint32_t i = 0; i < e.nfilters && byAll; i++) {
       const Filter& f = v.filters[e.filters + i];
-      bool excl = !((f.flags & FF_ZERO_RD) && !(f.flags & FF_USERINFO)) && condition_block(v, f, rv, nsl, true, nd);
+      bool fnd = false;
+      bool excl = !((f.flags & FF_ZERO_RD) && !(f.flags & FF_USERINFO)) && condition_block(v, f, rv, nsl, true, &fnd);
+      *nd = *nd | fnd;
       if (!excl) byAll = false;
+      else if (fnd) pend = true;
     }
-    if (byAll && e.nfilters > 0) return false;
+    if (byAll && e.nfilters > 0 && !pend) return false;
   }
   return true;
 }

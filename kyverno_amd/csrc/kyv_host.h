@@ -209,8 +209,23 @@ struct FailPath {  // decoded path record
   uint32_t key[2];
 };
 
+// The configuration an evaluation ran in (kyvgpu.h kyv_eval_plan / kyv_slice_plan, diagnostics): the ruleset's glob
+// masks (plan_ruleset, either backend) and, for a GPU evaluation, the lane tail tables, the match lists and the rule
+// slices as layout_schedule laid them out
+struct SlicePlan { uint32_t k0 = 0, k1 = 0, fused = 0, chunk = 0, cond = 0; };
+struct EvalPlan {
+  uint32_t gmask_patterns = 0, cond_sets = 0, gmask_words = 0, unmasked = 0;
+  uint32_t onemask = 0;
+  uint32_t tail_used[5] = {0, 0, 0, 0, 0};  // slots, namespace slots, wildcard requirements, annotation pairs, group /
+  uint32_t tail_cand[5] = {0, 0, 0, 0, 0};  // version atoms: table entries used, distinct candidates seen
+  uint32_t fast = 0, fasteval = 0, generic = 0;
+};
+void plan_ruleset(const Ruleset& rs, EvalPlan* p);
+
 struct Results {
   uint32_t nres = 0, nrules = 0;
+  EvalPlan plan;
+  std::vector<SlicePlan> slices;
   std::vector<uint8_t> status;      // [rule][res]
   std::vector<uint32_t> pss_fails;  // [rule][res] for PSS rules (empty otherwise)
   std::vector<FailRec> fails;

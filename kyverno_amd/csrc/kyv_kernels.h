@@ -359,7 +359,7 @@ KYV_HD __attribute__((always_inline)) void sel_prog(const SelProg& sp, const Lan
     const bool ok = (op == RQ_EQ || op == RQ_IN) ? inset : op == RQ_NOTIN ? (!has | !inset) : op == RQ_EXISTS ? has : !has;
     no = no | !ok;
   }
-  *nd = *nd | n;
+  *nd = *nd | (n & !err & !no);  // raised when the valid choice matches (check_selector)
   *r_out = err ? -1 : no ? 0 : 1;
 }
 KYV_HD __attribute__((always_inline)) SelProg ld_selprog(const SelProg* p) {
@@ -447,7 +447,7 @@ KYV_HD __attribute__((always_inline)) bool match_rule_rec(const View& v, const M
   const bool any = mm == MM_ANY, all = mm == MM_ALL || mm == MM_PLAIN;
   if (!any && !all) return false;
   const bool eany = em == MM_ANY || em == MM_PLAIN, eall = em == MM_ALL;
-  bool one = false, failed = false, excluded = false, byAll = true;
+  bool one = false, failed = false, excluded = false, byAll = true, pend = false;
   const uint32_t n = nmf + nef;
 #pragma unroll 1
   for (uint32_t j = 0; j < n; j++) {
@@ -464,19 +464,24 @@ KYV_HD __attribute__((always_inline)) bool match_rule_rec(const View& v, const M
     const MRecFilter F = Rp->f[j];
 #endif
     const bool skip = ism ? (F.bits & FF_ZERO_RD) != 0 : ((F.bits & FF_ZERO_RD) && !(F.bits & FF_USERINFO));
-    const bool c = !skip && cb_rec(v, F, mf, rv, labels, nsl, !ism, nd, tt, lt);
+    bool fnd = false;
+    const bool c = !skip && cb_rec(v, F, mf, rv, labels, nsl, !ism, &fnd, tt, lt);
+    *nd = *nd | fnd;
     if (ism) {
       if (any) { if (c) one = true; }
       else if (!c) failed = true;
-    } else if (eany) {
-      if (c) excluded = true;
+    } else if (eany) {  // (a filter that excludes on one map order only is pending: match_rule, kyv_eval.h)
+      if (c && !fnd) excluded = true;
+      else if (c) pend = true;
     } else if (!c) {
       byAll = false;
+    } else if (fnd) {
+      pend = true;
     }
   }
   if (any ? !one : failed) return false;
   if (eany && excluded) return false;
-  if (eall && byAll && nef > 0) return false;
+  if (eall && byAll && nef > 0 && !pend) return false;
   return true;
 }
 
@@ -560,24 +565,24 @@ KYV_HD __attribute__((always_inline)) bool match_fast(const View& v, uint32_t bi
   }
   const bool matched = any ? one : !failed;
   const bool eany = em == MM_ANY || em == MM_PLAIN, eall = em == MM_ALL;
-  bool excluded = false, byAll = true;
+  bool excluded = false, byAll = true, pend = false;  // pend: excluded on one map order only (match_rule, kyv_eval.h)
 #pragma unroll
   for (uint32_t j = 0; j < MREC_F; j++) {
     if (j >= nmf && j < nmf + nef && (eany || eall)) {
       const bool skip = (F[j].bits & FF_ZERO_RD) && !(F[j].bits & FF_USERINFO);
       const bool ev = matched & (eany ? !excluded : byAll);
-      bool c = false;
+      bool c = false, fnd = false;
       if (!skip) {
-        bool fnd;
         c = filt_fast(F[j], mf, tt, t, true, &fnd);
         n = n | (ev & fnd);
       }
-      if (eany) excluded = excluded | (ev & c);
+      if (eany) excluded = excluded | (ev & c & !fnd);
       else byAll = byAll & !(ev & !c);
+      pend = pend | (ev & c & fnd);
     }
   }
   *nd = *nd | n;
-  return matched & !(eany & excluded) & !(eall & byAll & (nef > 0));
+  return matched & !(eany & excluded) & !(eall & byAll & (nef > 0) & !pend);
 }
 
 // Pattern / anyPattern rules without preconditions (and compile-time fallback rules): the match phase is only

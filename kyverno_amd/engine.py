@@ -240,6 +240,25 @@ class Results:
             L.kyv_results_failures(self.h, out.ctypes.data, n)
         return out
 
+    TAIL_TABLES = ("slots", "ns_slots", "wildcards", "annotations", "group_versions")
+
+    def plan(self):
+        """The configuration this evaluation ran in (kyv_results_plan, diagnostics): the ruleset's glob masks
+        (`gmask_patterns`, `cond_sets`, `gmask_words`, `unmasked_literals`; either backend) and, zero on the CPU
+        backend, `onemask`, the lane tail tables as `tail_used` / `tail_candidates` dicts over TAIL_TABLES,
+        `fast_records`, `fasteval_records`, `generic_rules`, and `slices`: one dict per rule slice (`k0`, `k1`,
+        `fused_rules`, `chunk_rules`, `cond_rules`)"""
+        L = K.lib()
+        p = K.EvalPlan()
+        K.check(L.kyv_results_plan(self.h, ctypes.byref(p)))
+        out = {f: getattr(p, f) for f, _ in K.EvalPlan._fields_ if not f.startswith("tail_") and f != "slices"}
+        out["tail_used"] = dict(zip(self.TAIL_TABLES, list(p.tail_used)))
+        out["tail_candidates"] = dict(zip(self.TAIL_TABLES, list(p.tail_candidates)))
+        sl = (K.SlicePlan * max(1, p.slices))()
+        n = L.kyv_results_plan_slices(self.h, sl, p.slices)
+        out["slices"] = [{f: getattr(sl[i], f) for f, _ in K.SlicePlan._fields_} for i in range(min(n, p.slices))]
+        return out
+
     def fallback_reason(self, res, rule):
         """why pair (res, rule) is KYV_ST_FALLBACK ("" otherwise)"""
         buf = ctypes.create_string_buffer(512)

@@ -185,39 +185,43 @@ static bool valid_label_value(const std::string& v) { return v.empty() || qualif
 
 struct Req { std::string key, op; std::vector<std::string> vals; };
 
-// CheckSelector (pkg/utils/match/labels.go:10-24) incl. wildcards.ReplaceInSelector; returns 0 no match, 1 match,
-// -1 error (invalid selector), and flags nondeterminism when several labels can satisfy a wildcard entry.
-static int check_selector(const VP& sel, const std::map<std::string, std::string>& labels, bool* nd) {
-  if (isnil(sel)) return 0;
-  std::vector<Req> reqs;
-  VP ml = sel->get("matchLabels");
-  std::map<std::string, std::string> result;
-  if (ml && ml->t == T::Obj) {
-    for (auto& kv : ml->o) {
-      std::string k = kv.first, v = kv.second && kv.second->t == T::Str ? kv.second->s : "";
-      if (gou::contains_wildcard(k) || gou::contains_wildcard(v)) {
-        int n = 0;
-        std::string mk, mv;
-        for (auto& lv : labels)
-          if (gou::wildcard_match(k, lv.first) && gou::wildcard_match(v, lv.second)) {
-            if (n == 0) { mk = lv.first; mv = lv.second; }
-            n++;
-          }
-        if (n > 1 && nd) *nd = true;
-        if (n == 0) {
-          for (auto& c : k) if (c == '*' || c == '?') c = '0';
-          for (auto& c : v) if (c == '*' || c == '?') c = '0';
-          mk = k; mv = v;
-        }
-        if (result.count(mk) && nd) *nd = true;
-        result[mk] = mv;
-      } else {
-        if (result.count(k) && nd) *nd = true;
-        result[k] = v;
-      }
-    }
+// The reference's Go-map-order choices inside one rule's match evaluation, walked like an odometer: a selector whose
+// outcome depends on map order asks next(n) which of its n outcomes this run takes, and validate_policy_rules repeats
+// the match with advance() until every combination has been seen (or its cap is hit).
+struct Chooser {
+  std::vector<uint32_t> pick, arity;
+  size_t pos = 0;
+  uint32_t next(uint32_t n) {
+    if (pos == pick.size()) { pick.push_back(0); arity.push_back(n); }
+    arity[pos] = n;
+    const uint32_t c = pick[pos] < n ? pick[pos] : 0;
+    pos++;
+    return c;
   }
-  VP me = sel->get("matchExpressions");
+  bool advance() {
+    pos = 0;
+    while (!pick.empty()) {
+      if (pick.back() + 1 < arity.back()) { pick.back()++; return true; }
+      pick.pop_back();
+      arity.pop_back();
+    }
+    return false;
+  }
+};
+static thread_local Chooser* g_chooser = nullptr;
+struct ChooserScope {  // installs a Chooser for one enumeration; taken down on every way out of it
+  explicit ChooserScope(Chooser* c) { g_chooser = c; }
+  ~ChooserScope() { g_chooser = nullptr; }
+  ChooserScope(const ChooserScope&) = delete;
+  ChooserScope& operator=(const ChooserScope&) = delete;
+};
+constexpr size_t SEL_ENUM_CAP = 4096;  // selector maps enumerated per selector before it is flagged without looking on
+constexpr int MATCH_ENUM_CAP = 64;     // match evaluations per (rule, resource) pair
+
+// labels.go:10-24 after ReplaceInSelector produced `result`: LabelSelectorAsSelector + Matches; 1 match, 0 no, -1 error
+static int selector_outcome(const std::map<std::string, std::string>& result, const VP& me,
+                            const std::map<std::string, std::string>& labels) {
+  std::vector<Req> reqs;
   size_t nexpr = me && me->t == T::Arr ? me->a.size() : 0;
   if (result.empty() && nexpr == 0) return 1;  // Everything
   for (auto& kv : result) reqs.push_back(Req{kv.first, "=", {kv.second}});
@@ -251,6 +255,78 @@ static int check_selector(const VP& sel, const std::map<std::string, std::string
     if (!ok) return 0;
   }
   return 1;
+}
+
+// CheckSelector (pkg/utils/match/labels.go:10-24) incl. wildcards.ReplaceInSelector (wildcards.go:13-48); returns 0 no
+// match, 1 match, -1 error (invalid selector). Go map order enters twice: expandWildcards returns the FIRST label of
+// the resource that matches a wildcard matchLabels entry (any of its hits; the entry with '*' / '?' replaced by '0'
+// when there is none), and replaceWildcardsInMapKeyValues writes the entries into one result map in the order of the
+// pattern map, so of two entries that produce the same key either value can be the one that stays. Every choice is
+// enumerated. A mismatch and an error both leave the enclosing block unmatched (labels.go's callers append an error
+// either way), so the selector is flagged nondeterministic exactly when some choice matches and some other does not;
+// the outcome returned is then the one the enclosing enumeration (Chooser) asks for, the match outside one.
+static int check_selector(const VP& sel, const std::map<std::string, std::string>& labels, bool* nd) {
+  if (isnil(sel)) return 0;
+  VP ml = sel->get("matchLabels");
+  VP me = sel->get("matchExpressions");
+  std::vector<std::vector<std::pair<std::string, std::string>>> cand;  // per matchLabels entry: what it can become
+  if (ml && ml->t == T::Obj) {
+    for (auto& kv : ml->o) {
+      std::string k = kv.first, v = kv.second && kv.second->t == T::Str ? kv.second->s : "";
+      cand.emplace_back();
+      if (gou::contains_wildcard(k) || gou::contains_wildcard(v)) {
+        for (auto& lv : labels)
+          if (gou::wildcard_match(k, lv.first) && gou::wildcard_match(v, lv.second)) cand.back().push_back(lv);
+        if (cand.back().empty()) {
+          for (auto& c : k) if (c == '*' || c == '?') c = '0';
+          for (auto& c : v) if (c == '*' || c == '?') c = '0';
+          cand.back().push_back({k, v});
+        }
+      } else {
+        cand.back().push_back({k, v});
+      }
+    }
+  }
+  std::set<int> seen;
+  size_t budget = SEL_ENUM_CAP;
+  bool capped = false;
+  std::vector<size_t> at(cand.size(), 0);
+  for (;;) {
+    std::map<std::string, std::vector<std::string>> byKey;  // result key -> the distinct values written to it
+    for (size_t i = 0; i < cand.size(); i++) {
+      auto& vals = byKey[cand[i][at[i]].first];
+      if (std::find(vals.begin(), vals.end(), cand[i][at[i]].second) == vals.end()) vals.push_back(cand[i][at[i]].second);
+    }
+    std::vector<std::pair<std::string, size_t>> last;  // per key: which of its values was written last
+    for (auto& kv : byKey) last.push_back({kv.first, 0});
+    for (;;) {
+      if (budget == 0) { capped = true; break; }
+      budget--;
+      std::map<std::string, std::string> result;
+      for (auto& kl : last) result[kl.first] = byKey[kl.first][kl.second];
+      seen.insert(selector_outcome(result, me, labels));
+      size_t j = 0;
+      for (; j < last.size(); j++) {
+        if (++last[j].second < byKey[last[j].first].size()) break;
+        last[j].second = 0;
+      }
+      if (j == last.size()) break;
+    }
+    if (capped) break;
+    size_t i = 0;
+    for (; i < cand.size(); i++) {
+      if (++at[i] < cand[i].size()) break;
+      at[i] = 0;
+    }
+    if (i == cand.size()) break;
+  }
+  const int other = seen.count(0) || capped ? 0 : -1;
+  const bool matches = seen.count(1) || capped, fails = seen.count(0) || seen.count(-1) || capped;
+  if (matches && fails) {
+    if (nd) *nd = true;
+    return (g_chooser ? g_chooser->next(2) : 0) == 0 ? 1 : other;
+  }
+  return matches ? 1 : other;
 }
 
 // ---------------- match / exclude (pkg/engine/utils.go) ----------------
@@ -1211,23 +1287,40 @@ PolicyResult validate_policy_rules(const VP& policy, const std::vector<VP>& rule
   int applied = 0;
   for (auto& rule : rules) {
     if (!rule_has_validate(rule) && !has_nonempty(rule, "verifyImages")) continue;
-    bool nd = false;
-    bool m = matches_resource_description(rule, resource, nsLabels, &nd);
-    if (!m) m = matches_resource_description(rule, nullptr, nsLabels, &nd);  // OldResource retry (validation.go:606)
-    if (!m) continue;
-    if (!g_exceptions.empty()) {  // hasPolicyExceptions (validation.go:158-161)
-      const std::string pns = nested_string(policy, {"metadata", "namespace"});
-      const std::string rname = oj::get_str(rule, "name");
-      std::string key = matching_exception(pns.empty() ? pr.name : pns + "/" + pr.name, rname, resource, nsLabels, &nd);
-      if (!key.empty()) {
-        RuleResult rr;
-        rr.name = rname;
-        rr.status = "skip";
-        rr.message = "rule skipped due to policy exception " + key;
-        rr.nondeterministic = nd;
-        pr.rules.push_back(rr);
-        continue;
-      }
+    // Every combination of the match's map-order choices (Chooser): the pair has a response when some order matches,
+    // and it is nondeterministic when the orders disagree -- on the match, or on the exception that applies -- or when
+    // a selector consulted on the way had differing outcomes
+    bool nd = false, have = false, capped = false;
+    std::string key;
+    std::set<std::pair<bool, std::string>> outcomes;
+    const std::string pns = nested_string(policy, {"metadata", "namespace"});
+    const std::string rname = oj::get_str(rule, "name");
+    Chooser ch;
+    int runs = 0;
+    {
+    ChooserScope scope(&ch);
+    do {
+      ch.pos = 0;
+      bool m = matches_resource_description(rule, resource, nsLabels, &nd);
+      if (!m) m = matches_resource_description(rule, nullptr, nsLabels, &nd);  // OldResource retry (validation.go:606)
+      std::string k;
+      if (m && !g_exceptions.empty())  // hasPolicyExceptions (validation.go:158-161)
+        k = matching_exception(pns.empty() ? pr.name : pns + "/" + pr.name, rname, resource, nsLabels, &nd);
+      outcomes.insert({m, k});
+      if (m && !have) { have = true; key = k; }
+      if (++runs >= MATCH_ENUM_CAP) { capped = ch.advance(); break; }
+    } while (ch.advance());
+    }
+    if (!have) continue;
+    if (outcomes.size() > 1 || capped) nd = true;
+    if (!key.empty()) {
+      RuleResult rr;
+      rr.name = rname;
+      rr.status = "skip";
+      rr.message = "rule skipped due to policy exception " + key;
+      rr.nondeterministic = nd;
+      pr.rules.push_back(rr);
+      continue;
     }
     RuleResult rr = validate_rule(rule, resource);
     rr.nondeterministic |= nd;
