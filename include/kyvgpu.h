@@ -197,6 +197,24 @@ typedef struct kyv_wave_facts_out {
   size_t bits_len;
 } kyv_wave_facts_out;
 int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out);
+/* What the batch's order within a kind is made of (diagnostics, read-only). The batch order is (kind class, shape
+ * key, input index), ascending; the shape key of a resource packs, for each list position of the ruleset's patterns
+ * and foreach loops, the largest length of an array the resource has there, so that the 64 resources of a match wave
+ * have lists of about equal lengths. Buffers as in kyv_batch_wave_facts.
+ *   keys  [resources]  the key of each resource, by index in the caller's input: over `paths`, first path first,
+ *                      key = key << bits | min(length, 2^bits - 1), where length is the largest length of an array
+ *                      found at the path without its last "[*]" (0: none found; a "[*]" inside the path follows
+ *                      every element of an array). A resource too large for path columns has key 0.
+ *   paths              JSON {"bits": 3, "ordered": true, "paths": [path, ...]}: path segments as in
+ *                      kyv_batch_wave_facts. With KYV_SHAPE_ORDER=0 in the environment when the batch was built,
+ *                      "ordered" is false, every key is 0 and the order within a kind class is the input order.
+ * paths_len receives the JSON's full length. */
+typedef struct kyv_shape_keys_out {
+  uint64_t* keys; size_t keys_cap;
+  char* paths; size_t paths_cap;
+  size_t paths_len;
+} kyv_shape_keys_out;
+int kyv_batch_shape_keys(const kyv_batch* b, kyv_shape_keys_out* out);
 
 /* The batch builder's size guard, as it decides it: 1 when a path-column table of `entries` 8-byte entries (all
  * columns' rows together) can be built, 0 when kyv_batch_build refuses the batch ("split the batch"). Column offsets

@@ -66,7 +66,7 @@ EXPORTS = [
     "kyv_batch_export_failures", "kyv_comm_unique_id", "kyv_comm_init", "kyv_comm_free", "kyv_comm_gather_results",
     "kyv_comm_gathered_status", "kyv_comm_gathered_failures", "kyv_comm_gather_report", "kyv_comm_reduce_counts", "kyv_results_batch_ms",
     "kyv_calibrate_fetch", "kyv_batch_wave_facts", "kyv_col_entries_fit32", "kyv_results_plan",
-    "kyv_results_plan_slices",
+    "kyv_results_plan_slices", "kyv_batch_shape_keys",
 ]
 
 
@@ -74,6 +74,11 @@ class WaveFactsOut(ctypes.Structure):
     _fields_ = [("facts", ctypes.c_void_p), ("facts_cap", ctypes.c_size_t), ("hot", ctypes.c_void_p),
                 ("hot_cap", ctypes.c_size_t), ("order", ctypes.c_void_p), ("order_cap", ctypes.c_size_t),
                 ("bits", ctypes.c_void_p), ("bits_cap", ctypes.c_size_t), ("bits_len", ctypes.c_size_t)]
+
+
+class ShapeKeysOut(ctypes.Structure):
+    _fields_ = [("keys", ctypes.c_void_p), ("keys_cap", ctypes.c_size_t), ("paths", ctypes.c_void_p),
+                ("paths_cap", ctypes.c_size_t), ("paths_len", ctypes.c_size_t)]
 
 
 class EvalPlan(ctypes.Structure):
@@ -162,6 +167,7 @@ def lib():
     L.kyv_batch_num_resources.restype = u32
     L.kyv_batch_stats_get.argtypes = [vp, ctypes.POINTER(BatchStats)]
     L.kyv_batch_wave_facts.argtypes = [vp, ctypes.POINTER(WaveFactsOut)]
+    L.kyv_batch_shape_keys.argtypes = [vp, ctypes.POINTER(ShapeKeysOut)]
     L.kyv_eval.argtypes = [vp, vp, ctypes.POINTER(EvalOpts), ctypes.POINTER(vp)]
     L.kyv_results_free.argtypes = [vp]
     L.kyv_results_status.argtypes = [vp, ctypes.c_void_p, sz]

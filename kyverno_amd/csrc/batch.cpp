@@ -15,6 +15,7 @@
 #include <memory>
 #include <string_view>
 #include <thread>
+#include <unordered_set>
 
 #include "kyv_host.h"
 #include "kyv_pss.h"
@@ -763,22 +764,23 @@ KindGate rule_gate(const Ruleset& rs, const RuleDesc& rd) {
   return g;
 }
 
-// Stable sort of the headers by kind class + the per-class rule gate table.
-void order_by_kind(Batch& b) {
+void shape_keys(Batch& b, int threads);
+
+// Sort of the headers by (kind class, shape key, input index) + the per-class rule gate table. Classes keep their
+// first-occurrence order; Batch::shape_key empty = every key 0 (plain kind-major order). The permutation is a
+// function of the classes and keys alone, whatever the thread count.
+void order_by_kind(Batch& b, int threads) {
   const Ruleset& rs = *b.rs;
   size_t n = b.hdr.size(), nr = rs.rules.size();
   std::unordered_map<uint32_t, uint32_t> cls;  // gvk_kind sid -> class
   std::vector<uint32_t> cls_kind;
-  std::vector<uint32_t> cls_count;
   for (auto& h : b.hdr) {
     auto it = cls.find(h.gvk_kind);
     if (it == cls.end()) {
       it = cls.emplace(h.gvk_kind, (uint32_t)cls_kind.size()).first;
       cls_kind.push_back(h.gvk_kind);
-      cls_count.push_back(0);
     }
     h.kclass = it->second;
-    cls_count[it->second]++;
   }
   b.nclass = (uint32_t)cls_kind.size();
   b.gate_words = (uint32_t)((nr + 31) / 32);
@@ -790,20 +792,94 @@ void order_by_kind(Batch& b) {
       if (on) b.gate[(size_t)c * b.gate_words + k / 32] |= 1u << (k % 32);
     }
   }
-  // counting sort by class (stable)
-  std::vector<uint32_t> start(b.nclass + 1, 0);
-  for (uint32_t c = 0; c < b.nclass; c++) start[c + 1] = start[c] + cls_count[c];
   bulk_vector<ResHeader> sorted(n);
   b.order.resize(n);
   b.inv.resize(n);
-  for (size_t i = 0; i < n; i++) {
-    ResHeader h = b.hdr[i];
-    uint32_t pos = start[h.kclass]++;
-    h.orig = (uint32_t)i;
-    sorted[pos] = h;
-    b.order[pos] = (uint32_t)i;
-    b.inv[i] = pos;
+  if (n == 0) return;
+  const int T = std::max(1, threads);
+  const uint64_t* key = b.shape_key.empty() ? nullptr : b.shape_key.data();
+  using CK = std::pair<uint32_t, uint64_t>;  // (class, key)
+  auto ck = [&](size_t i) { return CK(b.hdr[i].kclass, key ? key[i] : 0); };
+  // distinct (class, key) pairs -> dense ranks in sorted order, collected per slice of the input
+  // (KYV_SHAPE_BUCKETS is a knob for the tests, not a tuning option: the most pairs the counting sort takes, default
+  // 65536, so that a small batch can be sent down the comparison sort; one getenv per batch build)
+  const char* mb = getenv("KYV_SHAPE_BUCKETS");
+  const size_t MAX_BUCKETS = mb && atoi(mb) > 0 ? (size_t)atoi(mb) : (size_t)1 << 16;
+  const size_t nch = std::max<size_t>(1, std::min<size_t>((size_t)T * 2, n / 4096 + 1));
+  auto lo_of = [&](size_t c) { return n * c / nch; };
+  std::vector<std::vector<CK>> local(nch);
+  std::atomic<bool> many{false};
+  parallel_for(nch, T, [&](size_t c) {
+    struct H { size_t operator()(const CK& p) const { return (size_t)((p.second ^ p.first) * 0x9E3779B97F4A7C15ull >> 17); } };
+    std::unordered_set<CK, H> seen;
+    CK last(NONE, 0);
+    for (size_t i = lo_of(c), e = lo_of(c + 1); i < e && !many.load(std::memory_order_relaxed); i++) {
+      const CK p = ck(i);
+      if (p == last) continue;
+      last = p;
+      if (seen.insert(p).second && seen.size() > MAX_BUCKETS) many = true;
+    }
+    local[c].assign(seen.begin(), seen.end());
+  });
+  std::vector<CK> pairs;
+  if (!many) {
+    for (auto& l : local) pairs.insert(pairs.end(), l.begin(), l.end());
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
   }
+  if (many || pairs.size() > MAX_BUCKETS) {  // too many distinct keys for counting: comparison sort (a total order)
+    for (size_t i = 0; i < n; i++) b.order[i] = (uint32_t)i;
+    std::sort(b.order.begin(), b.order.end(), [&](uint32_t x, uint32_t y) {
+      const CK px = ck(x), py = ck(y);
+      return px != py ? px < py : x < y;
+    });
+    parallel_for(nch, T, [&](size_t c) {
+      for (size_t pos = lo_of(c), e = lo_of(c + 1); pos < e; pos++) {
+        const uint32_t i = b.order[pos];
+        ResHeader h = b.hdr[i];
+        h.orig = i;
+        sorted[pos] = h;
+        b.inv[i] = (uint32_t)pos;
+      }
+    });
+    b.hdr.swap(sorted);
+    return;
+  }
+  // counting sort by rank (stable): per-slice histograms, exclusive prefix over (rank, slice), parallel scatter
+  const size_t nb = pairs.size();
+  std::vector<uint32_t> rank(n);
+  std::vector<std::vector<uint32_t>> start(nch, std::vector<uint32_t>(nb, 0));
+  parallel_for(nch, T, [&](size_t c) {
+    CK last(NONE, 0);
+    uint32_t rk = 0;
+    for (size_t i = lo_of(c), e = lo_of(c + 1); i < e; i++) {
+      const CK p = ck(i);
+      if (p != last) {
+        last = p;
+        rk = (uint32_t)(std::lower_bound(pairs.begin(), pairs.end(), p) - pairs.begin());
+      }
+      rank[i] = rk;
+      start[c][rk]++;
+    }
+  });
+  uint32_t at = 0;
+  for (size_t q = 0; q < nb; q++)
+    for (size_t c = 0; c < nch; c++) {
+      const uint32_t k = start[c][q];
+      start[c][q] = at;
+      at += k;
+    }
+  parallel_for(nch, T, [&](size_t c) {
+    uint32_t* st = start[c].data();
+    for (size_t i = lo_of(c), e = lo_of(c + 1); i < e; i++) {
+      ResHeader h = b.hdr[i];
+      const uint32_t pos = st[rank[i]]++;
+      h.orig = (uint32_t)i;
+      sorted[pos] = h;
+      b.order[pos] = (uint32_t)i;
+      b.inv[i] = pos;
+    }
+  });
   b.hdr.swap(sorted);
 }
 
@@ -1043,7 +1119,9 @@ Batch* build_batch(const Ruleset* rs, const char* json, size_t len, const char* 
     phase("remap");
     derive_strings(*b, 0, std::max(1, std::min(T, (int)(b->dict.strs.size() / 8192) + 1)));
     phase("strings");
-    order_by_kind(*b);
+    shape_keys(*b, T);
+    phase("shape-key");
+    order_by_kind(*b, T);
     phase("kind-order");
     resolve_path_columns(*b, T);
     // hot header plane (kyv_layout.h HotHdr): written last, the headers are final from here on
@@ -1228,6 +1306,93 @@ struct Resolver {
 };
 }  // namespace
 
+// Shape key (Batch::shape_key): the compiled kernels give a resource to a lane and loop over every list of a pattern
+// or foreach per lane, so a wave runs each loop to the longest list among its 64 resources. The key of a resource
+// packs, for each "[*]" position of the path trie, the largest length of an array the resource has there (0: no
+// array there), clamped to 7, 3 bits each; ordering a kind's resources by it puts equal list lengths side by side.
+std::vector<uint32_t> shape_key_nodes(const Ruleset& rs) {
+  std::vector<std::pair<uint32_t, uint32_t>> found;  // ("[*]" edges above the array, trie node that holds it)
+  std::function<void(uint32_t, uint32_t)> go = [&](uint32_t t, uint32_t depth) {
+    const Ruleset::TrieNode& T = rs.trie[t];
+    if (T.star != NONE) {
+      found.emplace_back(depth, t);
+      go(T.star, depth + 1);
+    }
+    for (const auto& kv : T.kids) go(kv.second, depth);
+  };
+  if (!rs.trie.empty()) go(0, 0);
+  std::sort(found.begin(), found.end());  // first-level lists first, then by depth; trie (node index) order within
+  if (found.size() > SHAPE_KEY_MAX_NODES) found.resize(SHAPE_KEY_MAX_NODES);  // the deepest do not fit
+  std::vector<uint32_t> out;
+  for (const auto& f : found) out.push_back(f.second);
+  return out;
+}
+
+namespace {
+// follows the trie as Resolver::go does, along the branches that lead to a key list only, and writes nothing
+struct ShapeWalk {
+  const Ruleset& rs;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> kids;  // per trie node: the (key sid, child) that lead on
+  std::vector<int8_t> field;   // trie node -> its field of the key, -1 none
+  std::vector<uint8_t> below;  // the elements of the array at this node lead on to another field
+  uint32_t nfields = 0;
+  explicit ShapeWalk(const Ruleset& r) : rs(r), kids(r.trie.size()), field(r.trie.size(), -1), below(r.trie.size(), 0) {
+    const std::vector<uint32_t> nodes = shape_key_nodes(rs);
+    nfields = (uint32_t)nodes.size();
+    for (uint32_t f = 0; f < nfields; f++) field[nodes[f]] = (int8_t)f;
+    std::function<bool(uint32_t)> leads = [&](uint32_t t) {
+      const Ruleset::TrieNode& T = rs.trie[t];
+      bool any = field[t] >= 0;
+      if (T.star != NONE && leads(T.star)) any = true, below[t] = 1;
+      for (const auto& kv : T.kids)
+        if (leads(kv.second)) any = true, kids[t].push_back(kv);
+      return any;
+    };
+    if (nfields) leads(0);
+  }
+  void go(const Node* R, uint32_t m, uint32_t t, uint8_t* len) const {
+    const Node mn = R[m];
+    if (node_type(mn) == N_MAP) {
+      for (const auto& kv : kids[t]) {
+        const uint32_t x = Resolver::find(R, mn, kv.first);
+        if (x != NONE) go(R, x, kv.second, len);
+      }
+    } else if (node_type(mn) == N_ARR && rs.trie[t].star != NONE) {
+      const int f = field[t];
+      if (f >= 0) len[f] = (uint8_t)std::max<uint32_t>(len[f], std::min<uint32_t>(mn.b, (1u << SHAPE_KEY_BITS) - 1));
+      if (below[t])
+        for (uint32_t i = 0; i < mn.b; i++) go(R, mn.a + i, rs.trie[t].star, len);
+    }
+  }
+};
+}  // namespace
+
+// runs on the headers in input order, before order_by_kind; KYV_SHAPE_ORDER=0: no keys (plain kind-major order).
+// The keys stay in the batch for kyv_batch_shape_keys (diagnostics): 8 B of host memory per resource, 80 MB at 10 M
+// beside a 23 GB batch image; they are not uploaded.
+void shape_keys(Batch& b, int threads) {
+  b.shape_key.clear();
+  const char* e = getenv("KYV_SHAPE_ORDER");
+  if (e && atoi(e) == 0) return;
+  const size_t n = b.hdr.size();
+  b.shape_key.assign(n, 0);
+  const ShapeWalk sw(*b.rs);
+  if (!sw.nfields || n == 0) return;
+  const size_t per = 4096;
+  parallel_for((n + per - 1) / per, std::max(1, threads), [&](size_t k) {
+    uint8_t len[SHAPE_KEY_MAX_NODES];
+    for (size_t r = k * per, end = std::min(n, r + per); r < end; r++) {
+      const ResHeader& h = b.hdr[r];
+      if (h.nnodes >= (1u << COL_TYPE_SHIFT)) continue;  // not column-eligible (resolve_path_columns): key 0
+      memset(len, 0, sw.nfields);
+      sw.go(b.nodes.data() + h.root, 0, 0, len);
+      uint64_t key = 0;
+      for (uint32_t f = 0; f < sw.nfields; f++) key = (key << SHAPE_KEY_BITS) | len[f];
+      b.shape_key[r] = key;
+    }
+  });
+}
+
 void resolve_path_columns(Batch& b, int threads) {
   const Ruleset& rs = *b.rs;
   size_t n = b.hdr.size();
@@ -1270,7 +1435,11 @@ void resolve_path_columns(Batch& b, int threads) {
     for (int t = 0; t < T; t++) th.emplace_back(work);
     for (auto& t : th) t.join();
   };
+  const auto tc0 = std::chrono::steady_clock::now();
   run(false, cnt);
+  if (getenv("KYV_DEBUG_STATS"))  // the shape-key pre-pass (shape_keys) is to stay cheaper than this pass
+    fprintf(stderr, "[kyvgpu] flatten %-12s %8.1f ms (within path-cols)\n", "col-count",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
   std::vector<std::vector<uint32_t>> base(nch, std::vector<uint32_t>(nsp, 0));
   std::vector<uint64_t> tot(nsp, 0);
   for (size_t c = 0; c < nch; c++)

@@ -288,6 +288,54 @@ int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out) {
   }
 }
 
+// the "[*]" paths a shape key is made of, most significant field first, as JSON (kyvgpu.h kyv_batch_shape_keys)
+static std::string shape_key_paths_json(const Ruleset& rs, bool ordered) {
+  const std::vector<uint32_t> nodes = shape_key_nodes(rs);
+  std::vector<std::string> node_path(rs.trie.size());
+  std::function<void(uint32_t, const std::string&)> go = [&](uint32_t t, const std::string& path) {
+    const Ruleset::TrieNode& T = rs.trie[t];
+    const std::string sep = path.empty() ? "" : ",";
+    if (T.star != NONE) {
+      node_path[t] = path + sep + "\"[*]\"";
+      go(T.star, node_path[t]);
+    }
+    for (const auto& kv : T.kids) {
+      std::string q = "\"";
+      for (unsigned char ch : rs.dict.strs[kv.first]) {
+        if (ch == '"' || ch == '\\') { q += '\\'; q += (char)ch; }
+        else if (ch < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", ch); q += b; }
+        else q += (char)ch;
+      }
+      go(kv.second, path + sep + q + "\"");
+    }
+  };
+  if (!rs.trie.empty()) go(0, "");
+  std::string js = "{\"bits\":" + std::to_string(SHAPE_KEY_BITS) + ",\"ordered\":" + (ordered ? "true" : "false") + ",\"paths\":[";
+  for (size_t i = 0; i < nodes.size(); i++) js += (i ? ",[" : "[") + node_path[nodes[i]] + "]";
+  return js + "]}";
+}
+
+int kyv_batch_shape_keys(const kyv_batch* b, kyv_shape_keys_out* out) {
+  if (!b || !out) return fail(KYV_EINVAL, "null argument");
+  try {
+    const Batch& x = *b->b;
+    const size_t n = x.hdr.size();
+    if (out->keys) {
+      if (out->keys_cap < n) return fail(KYV_EINVAL, "buffer too small");
+      for (size_t i = 0; i < n; i++) out->keys[i] = i < x.shape_key.size() ? x.shape_key[i] : 0;
+    }
+    const std::string js = shape_key_paths_json(*x.rs, x.shape_key.size() == n && n > 0);
+    out->paths_len = js.size();
+    if (out->paths) {
+      if (out->paths_cap < js.size() + 1) return fail(KYV_EINVAL, "buffer too small");
+      memcpy(out->paths, js.c_str(), js.size() + 1);
+    }
+    return KYV_OK;
+  } catch (std::exception& e) {
+    return fail(KYV_EINTERNAL, e.what());
+  }
+}
+
 int kyv_eval(const kyv_ruleset* rs, const kyv_batch* b, const kyv_eval_opts* opts, kyv_results** out) {
   if (!rs || !b || !out) return fail(KYV_EINVAL, "null argument");
   if (b->b->rs != rs->rs) return fail(KYV_EINVAL, "batch was built for a different ruleset");

@@ -188,8 +188,12 @@ struct Batch {
   std::vector<std::string> nsl_names;  // namespace name per set id
   // kind-major order: headers are sorted by kind class so that a wave's lanes share kind (and so mostly share
   // the rules that can match them); verdicts are produced in this order and un-permuted at the C ABI
+  // Within a kind class the resources are ordered by their shape key (batch.cpp shape_keys: the clamped lengths of
+  // the lists at the ruleset's "[*]" positions), so that the 64 lanes of a wave run their per-lane list loops for
+  // about the same number of iterations; equal keys keep input order. KYV_SHAPE_ORDER=0 at batch build: every key 0.
   std::vector<uint32_t> order;    // sorted position -> input index
   std::vector<uint32_t> inv;      // input index -> sorted position
+  std::vector<uint64_t> shape_key;  // input index -> shape key
   std::shared_ptr<const std::vector<uint32_t>> inv_shared;  // immutable copy handed to results (capi.cpp)
   std::vector<uint32_t> gate;     // [kclass][gate_words] bit k: rule k can match a resource of this class
   uint32_t gate_words = 0, nclass = 0;
@@ -281,6 +285,10 @@ KindGate rule_gate(const Ruleset& rs, const RuleDesc& rd);
 enum JitMode { JIT_AUTO = 0, JIT_OFF = 1, JIT_ON = 2 };
 constexpr size_t JIT_AUTO_MIN_RESOURCES = 65536;  // smaller batches are not worth a compile
 void resolve_path_columns(Batch& b, int threads);
+// the "[*]" trie nodes (the node that holds the array, TrieNode::star != NONE) a shape key is made of, most
+// significant field first: first-level lists in trie order, then the deeper ones by depth; 3 bits each, at most 21
+constexpr uint32_t SHAPE_KEY_BITS = 3, SHAPE_KEY_MAX_NODES = 64 / SHAPE_KEY_BITS;
+std::vector<uint32_t> shape_key_nodes(const Ruleset& rs);
 std::string format_path(const Ruleset& rs, const Batch& b, uint32_t tmpl, const uint16_t* idx, const uint32_t* key);
 
 }  // namespace kyv

@@ -119,7 +119,9 @@ class Batch:
         """What the flattener tells the compiled kernels about whole match waves (kyv_batch_wave_facts): a dict of
         `facts` uint32 [waves] (all-maps bits), `hot` uint32 [n, 4] (root, node count, flags, kind class per
         resource), `order` uint32 [n] (position in the batch's kind-major order -> input index) and the bits'
-        meaning, `maps`: one path (list of segments) per bit"""
+        meaning, `maps`: one path (list of segments) per bit; and what the order within a kind is made of
+        (kyv_batch_shape_keys): `shape_keys` uint64 [n] (input order), `shape_paths` (the list positions a key packs,
+        most significant first), `shape_bits` per position and `shape_ordered` (False: built with KYV_SHAPE_ORDER=0)"""
         L = K.lib()
         o = K.WaveFactsOut()
         K.check(L.kyv_batch_wave_facts(self.h, ctypes.byref(o)))
@@ -131,7 +133,15 @@ class Batch:
         o = K.WaveFactsOut(facts.ctypes.data, facts.size, hot.ctypes.data, hot.size, order.ctypes.data, order.size,
                            ctypes.addressof(bits), o.bits_len + 1, 0)
         K.check(L.kyv_batch_wave_facts(self.h, ctypes.byref(o)))
-        return dict(json.loads(bits.value.decode()), facts=facts, hot=hot, order=order)
+        sk = K.ShapeKeysOut()
+        K.check(L.kyv_batch_shape_keys(self.h, ctypes.byref(sk)))
+        keys = np.zeros(self.n, dtype=np.uint64)
+        paths = ctypes.create_string_buffer(sk.paths_len + 1)
+        sk = K.ShapeKeysOut(keys.ctypes.data, keys.size, ctypes.addressof(paths), sk.paths_len + 1, 0)
+        K.check(L.kyv_batch_shape_keys(self.h, ctypes.byref(sk)))
+        shape = json.loads(paths.value.decode())
+        return dict(json.loads(bits.value.decode()), facts=facts, hot=hot, order=order, shape_keys=keys,
+                    shape_paths=shape["paths"], shape_bits=shape["bits"], shape_ordered=shape["ordered"])
 
     def __del__(self):
         if getattr(self, "h", None):
