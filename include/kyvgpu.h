@@ -215,6 +215,30 @@ typedef struct kyv_shape_keys_out {
   size_t paths_len;
 } kyv_shape_keys_out;
 int kyv_batch_shape_keys(const kyv_batch* b, kyv_shape_keys_out* out);
+/* The batch's meta-key plane (diagnostics, read-only): for every meta-key class of the ruleset -- a wildcard metadata
+ * site of its pattern rules at the resource root (pos 0), spec.template (1) or spec.jobTemplate.spec.template (2) --
+ * and every resource, what the site's expansion gives: the status override, the key each wildcard resolved to and
+ * the entry of that key. The compiled walk reads these rows instead of resolving the keys in every evaluation.
+ * device < 0: the rows computed on the host; device >= 0: the rows that device filled before an evaluation of this
+ * batch took the compiled walk (KYV_EINVAL when it holds none). Buffers as in kyv_batch_wave_facts.
+ *   rows  [classes][resources][4]  the plane rows, resources in batch order (kyv_batch_wave_facts `order`):
+ *         word 0: override << 28 (0 none, else KYV_ST_PANIC / KYV_ST_FALLBACK / KYV_ST_ND) | dictionary id of the
+ *         first wildcard's key (the pattern key itself when no key of the resource matched);
+ *         one wildcard: word 1 = node type << 28 | node index of that key's entry (0xFFFFFFFF: none), word 2 = the
+ *         entry's string id; two wildcards: word 1 = the second key's id, words 2 and 3 = 0xE << 28 | node index of each
+ *         entry (0xFFFFFFFF: none)
+ *   desc  JSON {"classes": [{"pos": p, "labels": bool, "annotations": bool, "wild_labels": [glob, ...],
+ *         "wild_annotations": [glob, ...]}, ...], "rows": [[{"st": override, "keys": [string, ...],
+ *         "values": [string or null, ...]}, ...], ...]}: the classes, and the rows decoded (keys and the entries'
+ *         string values by their text; null: no entry, or not known without the node)
+ * classes receives the number of classes, desc_len the JSON's full length. */
+typedef struct kyv_meta_keys_out {
+  uint32_t* rows; size_t rows_cap;
+  char* desc; size_t desc_cap;
+  size_t desc_len;
+  uint32_t classes;
+} kyv_meta_keys_out;
+int kyv_batch_meta_keys(const kyv_batch* b, int device, kyv_meta_keys_out* out);
 
 /* The batch builder's size guard, as it decides it: 1 when a path-column table of `entries` 8-byte entries (all
  * columns' rows together) can be built, 0 when kyv_batch_build refuses the batch ("split the batch"). Column offsets
@@ -233,7 +257,8 @@ int64_t kyv_results_count(const kyv_results* r, int status);
 int kyv_results_rule_counts(const kyv_results* r, int64_t* out, size_t cap);
 double kyv_results_kernel_ms(const kyv_results* r);
 /* per-batch device work outside the evaluation (paid once per batch and device, before its first evaluation):
- * what = 0 the batch image upload (host -> HBM, ms), 1 the glob-mask kernel over the batch dictionary (ms) */
+ * what = 0 the batch image upload (host -> HBM, ms), 1 the glob-mask kernel over the batch dictionary (ms), 2 the
+ * meta-key plane's fill kernel (ms; 0 when no evaluation of the batch took a compiled walk that reads the plane) */
 double kyv_results_batch_ms(const kyv_results* r, int what);
 /* GPU evaluation time split by phase (HIP events on the evaluation stream, ms averaged over the launches):
  * out[0] verdict resets + match kernels, [1] compiled condition kernel, [2] pattern walk kernels (the dominant kernel

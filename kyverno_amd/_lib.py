@@ -66,7 +66,7 @@ EXPORTS = [
     "kyv_batch_export_failures", "kyv_comm_unique_id", "kyv_comm_init", "kyv_comm_free", "kyv_comm_gather_results",
     "kyv_comm_gathered_status", "kyv_comm_gathered_failures", "kyv_comm_gather_report", "kyv_comm_reduce_counts", "kyv_results_batch_ms",
     "kyv_calibrate_fetch", "kyv_batch_wave_facts", "kyv_col_entries_fit32", "kyv_results_plan",
-    "kyv_results_plan_slices", "kyv_batch_shape_keys",
+    "kyv_results_plan_slices", "kyv_batch_shape_keys", "kyv_batch_meta_keys",
 ]
 
 
@@ -79,6 +79,11 @@ class WaveFactsOut(ctypes.Structure):
 class ShapeKeysOut(ctypes.Structure):
     _fields_ = [("keys", ctypes.c_void_p), ("keys_cap", ctypes.c_size_t), ("paths", ctypes.c_void_p),
                 ("paths_cap", ctypes.c_size_t), ("paths_len", ctypes.c_size_t)]
+
+
+class MetaKeysOut(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("rows_cap", ctypes.c_size_t), ("desc", ctypes.c_void_p),
+                ("desc_cap", ctypes.c_size_t), ("desc_len", ctypes.c_size_t), ("classes", ctypes.c_uint32)]
 
 
 class EvalPlan(ctypes.Structure):
@@ -168,6 +173,7 @@ def lib():
     L.kyv_batch_stats_get.argtypes = [vp, ctypes.POINTER(BatchStats)]
     L.kyv_batch_wave_facts.argtypes = [vp, ctypes.POINTER(WaveFactsOut)]
     L.kyv_batch_shape_keys.argtypes = [vp, ctypes.POINTER(ShapeKeysOut)]
+    L.kyv_batch_meta_keys.argtypes = [vp, ctypes.c_int, ctypes.POINTER(MetaKeysOut)]
     L.kyv_eval.argtypes = [vp, vp, ctypes.POINTER(EvalOpts), ctypes.POINTER(vp)]
     L.kyv_results_free.argtypes = [vp]
     L.kyv_results_status.argtypes = [vp, ctypes.c_void_p, sz]

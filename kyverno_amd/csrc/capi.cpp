@@ -228,8 +228,82 @@ int kyv_batch_stats_get(const kyv_batch* b, kyv_batch_stats* out) {
   out->device_bytes = x.nodes.size() * sizeof(Node) + x.hdr.size() * sizeof(ResHeader) + x.hot.size() * sizeof(HotHdr) + x.heap.size() +
                       x.dict.strs.size() * (4 + 4 + 4 + 8 + 16 + 8) + x.faux.size() * sizeof(FloatAux) +
                       x.colv.size() * sizeof(uint64_t) + x.col_off.size() * 4 + x.gate.size() * 4 +
-                      (x.str_upper.size() + x.str_rx.size()) * 4;
+                      (x.str_upper.size() + x.str_rx.size()) * 4 + meta_key_plane_bytes(x);
   return KYV_OK;
+}
+
+// the classes and the decoded rows of a meta-key plane, as JSON (kyvgpu.h kyv_batch_meta_keys)
+static std::string meta_keys_json(const Ruleset& rs, const Batch& x, const std::vector<MetaKeyRow>& rows) {
+  auto quote = [](const std::string& s) {
+    std::string o = "\"";
+    for (unsigned char ch : s) {
+      if (ch == '"' || ch == '\\') { o += '\\'; o += (char)ch; }
+      else if (ch < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", ch); o += b; }
+      else o += (char)ch;
+    }
+    return o + "\"";
+  };
+  auto str = [&](uint32_t sid) { return sid < x.dict.strs.size() ? quote(x.dict.strs[sid]) : std::string("null"); };
+  const size_t n = x.hdr.size();
+  std::string js = "{\"classes\":[";
+  for (size_t c = 0; c < rs.meta_classes.size(); c++) {
+    const MetaClass& mc = rs.meta_classes[c];
+    js += std::string(c ? "," : "") + "{\"pos\":" + std::to_string(mc.pos) + ",\"labels\":" + (mc.site.has_labels ? "true" : "false") +
+          ",\"annotations\":" + (mc.site.has_ann ? "true" : "false") + ",\"wild_labels\":[";
+    for (uint32_t i = 0; i < mc.site.nwild_l; i++) js += (i ? "," : "") + str(rs.pool[mc.site.wild_l + 2 * i]);
+    js += "],\"wild_annotations\":[";
+    for (uint32_t i = 0; i < mc.site.nwild_a; i++) js += (i ? "," : "") + str(rs.pool[mc.site.wild_a + 2 * i]);
+    js += "]}";
+  }
+  js += "],\"rows\":[";
+  for (size_t c = 0; c < rs.meta_classes.size(); c++) {
+    const bool two = rs.meta_classes[c].site.nwild_l + rs.meta_classes[c].site.nwild_a > 1;
+    js += c ? ",[" : "[";
+    for (size_t r = 0; r < n; r++) {
+      const MetaKeyRow& q = rows[c * n + r];
+      js += std::string(r ? "," : "") + "{\"st\":" + std::to_string(q.w[0] >> MK_ST_SHIFT) + ",\"keys\":[" + str(q.w[0] & MK_KEY_MASK);
+      if (two) js += "," + str(q.w[1] & MK_KEY_MASK);
+      js += "],\"values\":[";
+      const ResHeader* hh = &x.hdr[r];
+      for (int s = 0; s < (two ? 2 : 1); s++) {
+        const uint32_t e = two ? q.w[2 + s] : q.w[1];
+        std::string val = "null";
+        if (e != NONE && (e & COL_INDEX_MASK) < hh->nnodes) {
+          const Node& nd = x.nodes[(size_t)hh->root + (e & COL_INDEX_MASK)];
+          if (node_type(nd) == N_STR) val = str(nd.a);
+        }
+        js += (s ? "," : "") + val;
+      }
+      js += "]}";
+    }
+    js += "]";
+  }
+  return js + "]}";
+}
+
+int kyv_batch_meta_keys(const kyv_batch* b, int device, kyv_meta_keys_out* out) {
+  if (!b || !out) return fail(KYV_EINVAL, "null argument");
+  try {
+    const Batch& x = *b->b;
+    const Ruleset& rs = *x.rs;
+    out->classes = (uint32_t)rs.meta_classes.size();
+    const size_t nrows = rs.meta_classes.size() * x.hdr.size();
+    std::vector<MetaKeyRow> rows = device < 0 ? meta_key_rows_host(rs, x) : meta_key_rows_device(x, device);
+    if (rows.size() != nrows) return fail(KYV_EINVAL, "the device holds no meta-key plane of this batch");
+    if (out->rows) {
+      if (out->rows_cap < 4 * nrows) return fail(KYV_EINVAL, "buffer too small");
+      if (nrows) memcpy(out->rows, rows.data(), nrows * sizeof(MetaKeyRow));
+    }
+    const std::string js = meta_keys_json(rs, x, rows);
+    out->desc_len = js.size();
+    if (out->desc) {
+      if (out->desc_cap < js.size() + 1) return fail(KYV_EINVAL, "buffer too small");
+      memcpy(out->desc, js.c_str(), js.size() + 1);
+    }
+    return KYV_OK;
+  } catch (std::exception& e) {
+    return fail(KYV_EINTERNAL, e.what());
+  }
 }
 
 // what the bits of a WaveFacts row stand for, as JSON (kyvgpu.h kyv_batch_wave_facts): the trie paths of
@@ -449,7 +523,7 @@ double kyv_calibrate_fetch(int device, uint64_t bytes, int mode) {
 }
 double kyv_results_batch_ms(const kyv_results* r, int what) {
   if (!r) return 0;
-  return what == 0 ? r->r.h2d_ms : what == 1 ? r->r.gmask_ms : 0;
+  return what == 0 ? r->r.h2d_ms : what == 1 ? r->r.gmask_ms : what == 2 ? r->r.meta_keys_ms : 0;
 }
 
 int kyv_results_phase_ms(const kyv_results* r, double* out, size_t cap) {

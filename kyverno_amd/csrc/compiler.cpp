@@ -2699,6 +2699,7 @@ void build_path_trie(Ruleset& rs) {
   // entries of pnodes that conflicted after their first visit assigned columns: clear the whole subtree
   // (a conflicting subtree is walked with t == NONE, which already cleared its entries' columns)
   assign_wave_facts(rs);
+  assign_meta_classes(rs);
 }
 
 // Per-wave facts (round 7, Batch::facts): what the flattener can tell the walk about a whole match wave of 64
@@ -2724,6 +2725,62 @@ void assign_wave_facts(Ruleset& rs) {
     if (map_child) spaces.insert(rs.col_rowspace[rs.pn_self[pn]]);
   }
   for (uint32_t s2 : spaces) if (rs.fact_spaces.size() < FACT_BITS) rs.fact_spaces.push_back(s2);
+}
+
+// Meta-key classes (round 10, kyv_layout.h MetaClass): the distinct wildcard metadata sites of pattern rules at a
+// static position (the positions of jit.cpp Gen::mark_paths: the pattern maps reached from a rule root by plain key
+// entries along "", spec.template or spec.jobTemplate.spec.template). A class is the position plus the site's
+// wildcard lists; rules with identical sites share one. A site elsewhere (below an array, another path), a site past
+// MAX_META_CLASSES, and a site with more than one wildcard per tag keep expand_meta in the walk.
+void assign_meta_classes(Ruleset& rs) {
+  rs.meta_classes.clear();
+  rs.meta_class_of.assign(rs.metas.size(), (int8_t)-1);
+  const uint32_t S = KSID(SPEC), T = KSID(TEMPLATE), J = KSID(JOBTEMPLATE);
+  std::function<void(uint32_t, uint32_t, const uint32_t*, int)> walk = [&](uint32_t pn, uint32_t mbase, const uint32_t* k, int depth) {
+    if (pn == NONE || pn >= rs.pnodes.size() || depth > 4) return;
+    const PNode& P = rs.pnodes[pn];
+    if (P.kind != P_MAP) return;
+    const int pos = depth == 0 ? 0 : (depth == 2 && k[0] == S && k[1] == T) ? 1 :
+                    (depth == 4 && k[0] == S && k[1] == J && k[2] == S && k[3] == T) ? 2 : -1;
+    if ((P.flags & PF_META) && pos >= 0 && (size_t)mbase + P.meta < rs.metas.size()) {
+      const MetaSite& ms = rs.metas[mbase + P.meta];
+      const uint32_t nw = ms.nwild_l + ms.nwild_a;
+      if (nw && ms.nwild_l <= 1 && ms.nwild_a <= 1 && nw <= (uint32_t)MAX_SLOTS) {
+        MetaClass mc{};
+        mc.pos = (uint32_t)pos;
+        mc.site = ms;
+        mc.site.slot_l = 0;
+        mc.site.slot_a = ms.nwild_l;
+        auto same = [&](const MetaClass& o) {
+          if (o.pos != mc.pos || o.site.has_labels != ms.has_labels || o.site.has_ann != ms.has_ann ||
+              o.site.nwild_l != ms.nwild_l || o.site.nwild_a != ms.nwild_a)
+            return false;
+          for (uint32_t i = 0; i < 2 * ms.nwild_l; i++) if (rs.pool[o.site.wild_l + i] != rs.pool[ms.wild_l + i]) return false;
+          for (uint32_t i = 0; i < 2 * ms.nwild_a; i++) if (rs.pool[o.site.wild_a + i] != rs.pool[ms.wild_a + i]) return false;
+          return true;
+        };
+        size_t c = 0;
+        while (c < rs.meta_classes.size() && !same(rs.meta_classes[c])) c++;
+        if (c == rs.meta_classes.size() && c < MAX_META_CLASSES) rs.meta_classes.push_back(mc);
+        if (c < rs.meta_classes.size()) rs.meta_class_of[mbase + P.meta] = (int8_t)c;
+      }
+    }
+    for (uint32_t e = 0; e < P.n; e++) {
+      const PEntry& E = rs.pentries[P.first + e];
+      if ((E.flags & EF_WILD) || E.child == NONE || E.handler == H_STAR || E.handler == H_NEGATION ||
+          E.handler == H_EXISTENCE || E.handler == H_EXIST_BADPAT)
+        continue;
+      uint32_t nk[4] = {k[0], k[1], k[2], k[3]};
+      if (depth < 4) nk[depth] = E.key;
+      walk(E.child, mbase, nk, depth + 1);
+    }
+  };
+  const uint32_t none[4] = {NONE, NONE, NONE, NONE};
+  for (const auto& rd : rs.rules) {
+    if (rd.kind == RK_PATTERN) walk(rd.root, rd.meta_sites, none, 0);
+    else if (rd.kind == RK_ANYPATTERN)
+      for (uint32_t a = 0; a < rd.nalts; a++) walk(rs.pool[rd.root + a], rd.meta_sites, none, 0);
+  }
 }
 
 }  // namespace kyv

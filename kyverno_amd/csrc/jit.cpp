@@ -35,6 +35,11 @@ namespace kyv {
 
 int pattern_depth(const Ruleset& rs, uint32_t pn, int guard);
 
+bool jit_meta_keys_on() {
+  const char* e = getenv("KYV_META_KEYS");
+  return !e || atoi(e) != 0;
+}
+
 namespace {
 
 struct Gen {
@@ -52,6 +57,24 @@ struct Gen {
   const size_t batch_max = getenv("KYV_JIT_BATCH") ? (size_t)std::max(1, atoi(getenv("KYV_JIT_BATCH"))) : 1;
   // leaf functions with a wave-uniform fast path for typed / absent values (node(), P_LEAF); KYV_JIT_LEAF_FAST=0: off
   const bool leaf_fast = !getenv("KYV_JIT_LEAF_FAST") || atoi(getenv("KYV_JIT_LEAF_FAST")) != 0;
+  // wildcard metadata sites with a meta-key class read their resolved keys and matched entries from the batch's
+  // meta-key plane (kyv_layout.h MetaKeyRow) instead of calling expand_meta; KYV_META_KEYS=0: off (the source of
+  // before round 10)
+  const bool meta_keys;
+  // A class site's plane row travels in its root scope's pc[] as two pseudo columns (MK_COL | class << 1 | half), so
+  // it is loaded in the root's preload round with the path columns. slot_meta[pnode]: pc[] index of the low half;
+  // wild_src[pentry]: where an EF_WILD entry of the labels / annotations map below such a site finds its entry
+  static constexpr uint32_t MK_COL = 0x80000000u;
+  struct WildSrc { int pc = -1; bool two = false; uint32_t cs = 0; };
+  std::vector<int> slot_meta;
+  std::vector<WildSrc> wild_src;
+  WildSrc cur_src[MAX_SLOTS];
+  int class_of(uint32_t pn) const {
+    const PNode& P = rs.pnodes[pn];
+    if (!meta_keys || !(P.flags & PF_META) || node_mbase[pn] == NONE || meta_pos[pn] < 0) return -1;
+    const size_t s = (size_t)node_mbase[pn] + P.meta;
+    return s < rs.meta_class_of.size() ? rs.meta_class_of[s] : -1;
+  }
 
   // Column scopes: the pattern root and every array-element pattern open a scope (one row of one row space);
   // every column lookup of the maps inside a scope (not crossing into array elements) is loaded up front by
@@ -65,8 +88,9 @@ struct Gen {
   std::vector<int8_t> meta_pos;                  // pnode -> static position whose metadata flags the flattener
                                                  // computed: 0 root, 1 spec.template, 2 spec.jobTemplate.spec.template
 
-  explicit Gen(const Ruleset& r)
-      : rs(r), emitted(r.pnodes.size(), 0), slot(r.pentries.size(), -1), slot_alen(r.pnodes.size(), -1),
+  explicit Gen(const Ruleset& r, int meta_keys_mode = -1)
+      : rs(r), meta_keys(meta_keys_mode < 0 ? jit_meta_keys_on() : meta_keys_mode != 0), emitted(r.pnodes.size(), 0), slot_meta(r.pnodes.size(), -1), wild_src(r.pentries.size()),
+        slot(r.pentries.size(), -1), slot_alen(r.pnodes.size(), -1),
         slot_elen(r.pentries.size(), -1), scope_of(r.pnodes.size()), scoped(r.pnodes.size(), 0),
         node_mbase(r.pnodes.size(), NONE), meta_pos(r.pnodes.size(), -1) {}
 
@@ -107,9 +131,20 @@ struct Gen {
       return;  // its elements open their own scopes
     }
     if (P.kind != P_MAP) return;
+    const int cls = class_of(pn);
+    if (cls >= 0) {  // (a static position is reached through maps only: this is the pattern root's scope, row = resource)
+      if (slot_meta[pn] >= 0) { ok = false; return; }
+      slot_meta[pn] = add(list, MK_COL | ((uint32_t)cls << 1));
+      add(list, MK_COL | ((uint32_t)cls << 1) | 1u);
+      const MetaSite& ms = rs.metas[node_mbase[pn] + P.meta];
+      const bool two = ms.nwild_l + ms.nwild_a > 1;
+      if (ms.nwild_l && ms.slot_l < (uint32_t)MAX_SLOTS) cur_src[ms.slot_l] = WildSrc{slot_meta[pn], two, 0u};
+      if (ms.nwild_a && ms.slot_a < (uint32_t)MAX_SLOTS) cur_src[ms.slot_a] = WildSrc{slot_meta[pn], two, ms.nwild_l};
+    }
     for (uint32_t e = 0; e < P.n; e++) {
       const uint32_t ei = P.first + e;
       const PEntry& E = rs.pentries[ei];
+      if ((E.flags & EF_WILD) && E.col == NONE && E.slot < (uint32_t)MAX_SLOTS && cur_src[E.slot].pc >= 0) wild_src[ei] = cur_src[E.slot];
       if (E.col != NONE) {
         if (slot[ei] >= 0) { ok = false; continue; }  // entry reached from two scopes: leave the rule interpreted
         slot[ei] = add(list, E.col);
@@ -127,6 +162,7 @@ struct Gen {
   void scope(uint32_t root) {
     if (root == NONE || root >= rs.pnodes.size() || scoped[root]) return;
     scoped[root] = 1;
+    for (auto& c : cur_src) c = WildSrc{};
     collect(root, scope_of[root], 0);
   }
   // open the scopes of every array-element pattern below pn
@@ -164,7 +200,18 @@ struct Gen {
     const auto& L = scope_of[root];
     std::ostringstream o;
     o << "uint64_t " << name << "[" << std::max<size_t>(1, L.size()) << "];";
-    for (size_t i = 0; i < L.size(); i++) o << " " << name << "[" << i << "] = " << rd << u(L[i]) << ", " << rowx << ");";
+    for (size_t i = 0; i < L.size(); i++) {
+      if (L[i] & MK_COL) { o << meta_load(L, i, name, rowx); continue; }
+      o << " " << name << "[" << i << "] = " << rd << u(L[i]) << ", " << rowx << ");";
+    }
+    return o.str();
+  }
+  // the two pc[] entries of a class site's plane row (root scopes only: `v` is the root function's View)
+  static std::string meta_load(const std::vector<uint32_t>& L, size_t i, const std::string& name, const std::string& rowx) {
+    if (L[i] & 1u) return std::string();  // the high half: set with the low one
+    std::ostringstream o;
+    o << " { const kyv_u32x4 mq = jc_meta(v, " << u((L[i] & ~MK_COL) >> 1) << ", " << rowx << "); " << name << "[" << i
+      << "] = (uint64_t)mq.x | ((uint64_t)mq.y << 32); " << name << "[" << i + 1 << "] = (uint64_t)mq.z | ((uint64_t)mq.w << 32); }";
     return o.str();
   }
 
@@ -417,6 +464,14 @@ struct Gen {
     if (E.col != NONE) {
       if (slot[ei] < 0) { ok = false; return; }  // every column entry belongs to a collected scope
       out << "  c" << e << " = jdec(pc[" << slot[ei] << "], &t" << e << ", &a" << e << ");\n";
+    } else if (wild_src[ei].pc >= 0) {
+      // the entry of the resolved key, found once per batch with the key (meta-key plane row, kyv_layout.h MetaKeyRow)
+      const WildSrc& ws = wild_src[ei];
+      if (ws.two)
+        out << "  c" << e << " = jdec((uint64_t)(uint32_t)(pc[" << ws.pc + 1 << "] >> " << 32u * ws.cs << "), &t" << e << ", &a" << e
+            << ");\n";
+      else
+        out << "  c" << e << " = jdec((pc[" << ws.pc << "] >> 32) | (pc[" << ws.pc + 1 << "] << 32), &t" << e << ", &a" << e << ");\n";
     } else {
       std::string key = (E.flags & EF_WILD) ? "w.keys.get(" + u(E.slot) + ")" : u(E.key);
       out << "  c" << e << " = wmap_find(w.R, " << keyexpr_rowvar << ".a, " << keyexpr_rowvar << ".b, " << key
@@ -425,7 +480,12 @@ struct Gen {
   }
 
   void map(uint32_t pn, const PNode& P) {
-    const bool needrow = (P.flags & PF_NEEDROW) != 0;
+    bool needrow = (P.flags & PF_NEEDROW) != 0;
+    if (needrow && meta_keys) {  // a map whose only column-less entries are found through the meta-key plane needs no row
+      needrow = false;
+      for (uint32_t e = 0; e < P.n; e++)
+        needrow = needrow || (rs.pentries[P.first + e].col == NONE && wild_src[P.first + e].pc < 0);
+    }
     const std::string T = u(P.tmpl);
     out << "  Node m{0u, 0u, 0u, 0u};\n";
     out << "  if (rn != NONE && " << (needrow ? "true" : "rt == T_UNK") << ") { m = gnode(w.R + rn); rt = node_type(m); }\n";
@@ -434,7 +494,7 @@ struct Gen {
     for (uint32_t e = 0; e < P.n; e++) {
       out << "  uint32_t c" << e << " = NONE, t" << e << " = T_UNK, a" << e << " = 0u;\n";
       const PEntry& E = rs.pentries[P.first + e];
-      if (E.col != NONE) lookup(P.first + e, e, "m");
+      if (E.col != NONE || wild_src[P.first + e].pc >= 0) lookup(P.first + e, e, "m");
     }
     (void)pn;
     // AnchorMap.CheckAnchorInResource (anchormap.go:30-44); wildcard keys use the slots as they are before
@@ -444,7 +504,8 @@ struct Gen {
       if (E.abit == 0xFF) continue;
       std::string B = "(1ull << " + std::to_string(E.abit) + ")";
       out << "  w.seen |= " << B << ";\n";
-      if (E.col != NONE) {
+      if (E.col != NONE || wild_src[P.first + e].pc >= 0) {
+        // (a plane-sourced entry: its map has no expansion site of its own, so the slot is already final here)
         out << "  if (c" << e << " != NONE) w.found |= " << B << ";\n";
       } else {
         std::string key = (E.flags & EF_WILD) ? "w.keys.get(" + u(E.slot) + ")" : u(E.key);
@@ -453,7 +514,23 @@ struct Gen {
     }
     const MetaSite* site =
         (P.flags & PF_META) && node_mbase[pn] != NONE && meta_pos[pn] >= 0 ? &rs.metas[node_mbase[pn] + P.meta] : nullptr;
-    if (site && site->nwild_l == 0 && site->nwild_a == 0) {
+    if (site && slot_meta[pn] >= 0) {
+      // wildcard keys of a site with a meta-key class: the override expand_meta would return and the key slots, from
+      // the plane row preloaded with the root scope's columns
+      const int S = slot_meta[pn];
+      const bool two = site->nwild_l + site->nwild_a > 1;
+      // (the class number is part of the function's text, hence of the pattern's shape: two rules whose patterns differ
+      // only in the glob have different classes, and must not share one root function and its plane-row load)
+      out << "  { const uint32_t mk0 = (uint32_t)pc[" << S << "];  // meta-key class " << class_of(pn) << "\n";
+      for (int tag = 0; tag < 2; tag++) {
+        if (!(tag == 0 ? site->nwild_l : site->nwild_a)) continue;
+        const uint32_t cs = tag == 0 ? 0u : site->nwild_l;
+        out << "    w.keys.set(" << u(tag == 0 ? site->slot_l : site->slot_a) << ", "
+            << (cs == 0 ? std::string("mk0 & MK_KEY_MASK") : "(uint32_t)(pc[" + std::to_string(S) + "] >> 32) & MK_KEY_MASK") << ");\n";
+      }
+      (void)two;
+      out << "    if (mk0 >> MK_ST_SHIFT) { w.ost = (uint8_t)(mk0 >> MK_ST_SHIFT); return ok_ret(); } }\n";
+    } else if (site && site->nwild_l == 0 && site->nwild_a == 0) {
       // ExpandInMetadata without wildcard keys at the root or a pod-template position: only its type assertions,
       // decided from the header flags the flattener computed for that position (same order as expand_meta:
       // absent/null metadata, non-object, anchor-like keys, labels / annotations that are not objects of strings)
@@ -481,7 +558,7 @@ struct Gen {
       const PEntry& E = rs.pentries[P.first + e];
       const std::string ET = u(E.tmpl);
       const std::string c = "c" + std::to_string(e), t = "t" + std::to_string(e);
-      if (E.col == NONE) lookup(P.first + e, e, "m");
+      if (E.col == NONE && wild_src[P.first + e].pc < 0) lookup(P.first + e, e, "m");
       auto call = [&](const std::string& wrap) {
         out << "    { Ret r = p" << E.child << "(w, " << c << ", " << t << ", a" << e << ", row, pc);\n"
             << "      if (w.ost) return r;\n"
@@ -1356,8 +1433,8 @@ static std::string meta_signature(const Ruleset& rs, const RuleDesc& rd) {
 }
 
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond,
-                       std::vector<uint16_t>* jit_shape) {
-  Gen g(rs);
+                       std::vector<uint16_t>* jit_shape, int meta_keys) {
+  Gen g(rs, meta_keys);
   jit_rules->assign(rs.rules.size(), 0);
   if (jit_shape) jit_shape->assign(rs.rules.size(), 0);
   if (jit_cond) jit_cond->assign(rs.rules.size(), 0);
@@ -1513,7 +1590,10 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
       case P_MAP: {
         if (P.flags & PF_META) {
           const MetaSite& ms = rs.metas[mbase + P.meta];
-          if (ms.nwild_l + ms.nwild_a) return true;
+          // (a site with a meta-key class reads the plane: no expand_meta, no register need beyond a light rule's)
+          const bool planed = g.meta_keys && pn < g.meta_pos.size() && g.meta_pos[pn] >= 0 && mbase + P.meta < rs.meta_class_of.size() &&
+                              rs.meta_class_of[mbase + P.meta] >= 0;
+          if ((ms.nwild_l + ms.nwild_a) && !planed) return true;
         }
         for (uint32_t e = 0; e < P.n; e++) {
           const PEntry& E = rs.pentries[P.first + e];
@@ -1668,7 +1748,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         }
       }
       std::vector<uint32_t> cand;
-      for (const auto& e : cnt) if (e.second >= 2) cand.push_back(e.first);
+      for (const auto& e : cnt) if (e.second >= 2 && !(e.first & Gen::MK_COL)) cand.push_back(e.first);
       std::stable_sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) { return cnt[a] > cnt[b]; });
       std::vector<std::vector<uint32_t>> slots;
       for (uint32_t c : cand) {
@@ -1700,6 +1780,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         for (size_t i = 0; i < L.size(); i++) {
           auto it = cslot.find(L[i]);
           if (it != cslot.end()) src << " pc[" << i << "] = jcc[" << it->second * 64u << "u + lane];";
+          else if (L[i] & Gen::MK_COL) src << Gen::meta_load(L, i, "pc", "row");
           else src << " pc[" << i << "] = jc_col(v, " << Gen::u(L[i]) << ", row);";
         }
         src << "\n"

@@ -213,7 +213,7 @@ struct DevRuleset {
   uint8_t* base = nullptr;
   size_t bytes = 0;
   size_t o_rules, o_filters, o_kinds, o_sels, o_reqs, o_pn, o_pe, o_leaves, o_atoms, o_metas, o_pss, o_pool, o_cnodes, o_conds, o_cprogs,
-      o_gpats, o_gsets;
+      o_gpats, o_gsets, o_mclasses;
   hipModule_t jmod = nullptr;     // runtime-compiled walk kernels (jit.cpp) loaded on this device
   std::vector<hipFunction_t> jfns;  // kyv_jit_walk_<g> per rule group
   std::vector<hipFunction_t> ffns;  // kyv_jit_fused_<g> per rule group, or null (the group has no fused rule)
@@ -419,6 +419,7 @@ struct DeviceResults {
   View* view = nullptr;  // device copy of the View the kernel reads
   // its fields the run-time switches set (KYV_HOTHDR, KYV_FACT_*): a later evaluation under other settings uploads
   // the View again
+  const MetaKeyRow* view_meta = nullptr;
   const HotHdr* view_hot = nullptr;
   uint32_t view_fact_and = 0;
   // pattern-shape tables (kyv_jit_shapes, round 5): [shape][res] verdict bytes and records, the per-class shape gate
@@ -469,6 +470,11 @@ struct DevBatch {
   uint32_t* order = nullptr;   // of device-resident results (export_status / export_failures)
   double upload_ms = 0;
   double gmask_ms = 0;  // glob-mask kernel of this batch (once per batch and device), HIP events
+  // meta-key plane (kyv_layout.h MetaKeyRow) [class][resource], filled once per batch and device by meta_keys_kernel
+  // before the first evaluation that takes the compiled walk of a source generated with it; its kernel's time
+  MetaKeyRow* meta_rows = nullptr;
+  size_t meta_bytes = 0;
+  double meta_ms = 0;
 };
 
 static DevRuleset* upload_ruleset(const Ruleset& rs, int device) {
@@ -497,6 +503,7 @@ static DevRuleset* upload_ruleset(const Ruleset& rs, int device) {
   for (size_t q = 0; q < rs.gsets.size(); q++) gs[q + 1] = gs[q] + (uint32_t)rs.gsets[q].size();
   for (auto& st : rs.gsets) gs.insert(gs.end(), st.begin(), st.end());
   d->o_gsets = p.add(gs);
+  d->o_mclasses = p.add(rs.meta_classes);
   d->bytes = p.size;
   HIP_OK(hipMalloc(&d->base, d->bytes));
   HIP_OK(p.copy_to(d->base));
@@ -572,6 +579,7 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
     v.str_rx = db->o_srx == SIZE_MAX ? nullptr : (const uint32_t*)(bbase + db->o_srx);
     v.str_gmask = db->gmask;
     v.gmask_words = db->gmask_words;
+    v.meta_rows = db->meta_rows;
   } else {
     v.str_gmask = nullptr;
     v.gmask_words = 0;
@@ -855,6 +863,17 @@ __global__ void __launch_bounds__(256) calib_gather_kernel(const uint4* __restri
 
 // condition sets (compiler.cpp assign_cond_sets): bit ng + q = wild2(s, e) for some literal e of set q (kyv_cond.h wild2,
 // both match directions)
+// The meta-key plane: one thread per (class, resource), rows [class][resource in batch order] (kyv_eval.h meta_key_row)
+__global__ void __launch_bounds__(256) meta_keys_kernel(const View* __restrict__ vp, const MetaClass* __restrict__ mcs,
+                                                        uint32_t ncls, MetaKeyRow* __restrict__ rows) {
+  const View& v = *vp;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (v.nres == 0 || i >= (size_t)ncls * v.nres) return;
+  const uint32_t cls = (uint32_t)(i / v.nres), r = (uint32_t)(i % v.nres);
+  const ResHeader h = v.hdr[r];
+  rows[i] = meta_key_row(v, mcs[cls], NodeTab{v.nodes + h.root}, h);
+}
+
 __global__ void __launch_bounds__(256) gmask_kernel(const View* __restrict__ vp, const uint32_t* __restrict__ gpats,
                                                     uint32_t ng, const uint32_t* __restrict__ gsets, uint32_t nsets,
                                                     uint32_t nstr, uint32_t words, uint32_t* __restrict__ out) {
@@ -934,7 +953,8 @@ static bool ensure_jit(Ruleset& rs, DevRuleset* dr) {
   if (!rs.jit_tried) {
     rs.jit_tried = true;
     try {
-      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape);
+      rs.jit_meta_keys = jit_meta_keys_on() && !rs.meta_classes.empty();
+      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape, rs.jit_meta_keys ? 1 : 0);
       rs.jit_nshapes = 0;
       for (auto x : rs.jit_shape) rs.jit_nshapes = std::max<uint32_t>(rs.jit_nshapes, x);
       bool any = false;
@@ -1006,7 +1026,8 @@ static bool ensure_jit_acct(Ruleset& rs, DevRuleset* dr) {
   std::lock_guard<std::mutex> lk(g_jit_mu);
   if (rs.jit_code_acct.empty()) {
     std::vector<uint8_t> jr, jc;
-    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc), nullptr, true);
+    // (the switch as the product source had it: the accounting kernels read the plane exactly when it is filled)
+    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc, nullptr, rs.jit_meta_keys ? 1 : 0), nullptr, true);
   }
   HIP_OK(hipModuleLoadData(&dr->amod, rs.jit_code_acct.data()));
   dr->afns.resize(dr->jfns.size());
@@ -1750,6 +1771,33 @@ static void layout_schedule(const Ruleset& rs, const Batch& b, const DevRuleset*
       if (rs.jit_rules[k] && jit_rule_fused(rs, k) && dr->ffns[rs.jit_rules[k] - 1]) sl.plan.fused++;
 }
 
+std::vector<MetaKeyRow> meta_key_rows_host(const Ruleset& rs, const Batch& b) {
+  const View v = make_view(rs, b, nullptr, nullptr, nullptr, nullptr);
+  const size_t n = b.hdr.size();
+  std::vector<MetaKeyRow> rows(rs.meta_classes.size() * n);
+  for (size_t c = 0; c < rs.meta_classes.size(); c++)
+    for (size_t r = 0; r < n; r++) {
+      const ResHeader& h = b.hdr[r];
+      rows[c * n + r] = meta_key_row(v, rs.meta_classes[c], NodeTab{v.nodes + h.root}, h);
+    }
+  return rows;
+}
+std::vector<MetaKeyRow> meta_key_rows_device(const Batch& b, int device) {
+  std::vector<MetaKeyRow> rows;
+  if (device < 0 || device >= (int)b.dev.size() || !b.dev[device]) return rows;
+  const DevBatch* db = (const DevBatch*)b.dev[device];
+  if (!db->meta_rows) return rows;
+  HIP_OK(hipSetDevice(device));
+  rows.resize(db->meta_bytes / sizeof(MetaKeyRow));
+  HIP_OK(hipMemcpy(rows.data(), db->meta_rows, db->meta_bytes, hipMemcpyDeviceToHost));
+  return rows;
+}
+size_t meta_key_plane_bytes(const Batch& b) {
+  size_t n = 0;
+  for (void* p : b.dev) if (p && ((const DevBatch*)p)->meta_rows) n = std::max(n, ((const DevBatch*)p)->meta_bytes);
+  return n;
+}
+
 // accumulate one slice's phase times (ms) from its events; `start`: the evaluation's start event for the first slice
 // (the verdict resets count to the match phase), the slice's own start event for the others
 static void slice_phases(const SliceSched& sl, hipEvent_t start, double* phase) {
@@ -1898,6 +1946,32 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
   hipStream_t stream = d.stream;
   const bool use_jit = jit_mode == JIT_ON || (jit_mode == JIT_AUTO && nres >= JIT_AUTO_MIN_RESOURCES);
   const bool jit = use_jit && ensure_jit(mrs, dr);
+  if (jit && rs.jit_meta_keys && !db->meta_rows && nres) {
+    // the meta-key plane of this batch (once per batch and device, after the glob masks it reads): only an evaluation
+    // that takes the compiled walk pays for it; the interpreted kernels keep expand_meta
+    const size_t nrows = rs.meta_classes.size() * nres;
+    db->meta_bytes = nrows * sizeof(MetaKeyRow);
+    HIP_OK(dmalloc(&db->meta_rows, db->meta_bytes));
+    hipEvent_t g0, g1;
+    HIP_OK(hipEventCreate(&g0));
+    HIP_OK(hipEventCreate(&g1));
+    HIP_OK(hipEventRecord(g0, 0));
+    hipLaunchKernelGGL(meta_keys_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, 0, (const View*)d.view,
+                       (const MetaClass*)(dr->base + dr->o_mclasses), (uint32_t)rs.meta_classes.size(), db->meta_rows);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(g1, 0));
+    HIP_OK(hipDeviceSynchronize());
+    float gms = 0;
+    HIP_OK(hipEventElapsedTime(&gms, g0, g1));
+    db->meta_ms = gms;
+    (void)hipEventDestroy(g0);
+    (void)hipEventDestroy(g1);
+  }
+  if (d.view_meta != db->meta_rows) {
+    v.meta_rows = db->meta_rows;
+    HIP_OK(hipMemcpy(d.view, &v, sizeof(View), hipMemcpyHostToDevice));
+    d.view_meta = db->meta_rows;
+  }
   for (auto& sl : d.slices)
     if (sl.jit_state != (int)jit) layout_schedule(rs, b, dr, d, sl, jit);
   if (d.shape_state != (int)jit) setup_shapes(rs, b, d, jit && dr->jshapes);
@@ -2226,6 +2300,7 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     out->jit_used = (jit ? 1 : 0) | (jit && cond ? 2 : 0) | (jit && d.nshapes ? 4 : 0);
     out->h2d_ms = db->upload_ms;
     out->gmask_ms = db->gmask_ms;
+    out->meta_keys_ms = db->meta_ms;
     if (!d.plan_ruleset_done) {  // a walk over the ruleset dictionary: once per batch, not per evaluation
       plan_ruleset(rs, &d.plan);
       d.plan_ruleset_done = true;
@@ -2897,6 +2972,7 @@ void free_device_images(Ruleset& rs, Batch* b) {
         hipSetDevice(d->device);
         dfree(d->base);
         dfree(d->gmask);
+        dfree(d->meta_rows);
         dfree(d->inv);
         dfree(d->order);
         if (d->out) { free_dev_results(*d->out, d->device); delete d->out; }

@@ -127,6 +127,8 @@ struct View {
   const uint32_t* str_rx;     // [string] regex_match bits of the ruleset's regexes (RX_FB: outside printable ASCII)
   const uint64_t* colv;     // path columns (kyv_layout.h): colv[col_off[c] + row]
   const uint32_t* col_off;  // (device View: pe[].col already holds col_off[col])
+  const MetaKeyRow* meta_rows;  // meta-key plane [class][nres] (kyv_layout.h), or nullptr: not filled (the compiled
+                                // kernels of a source generated with the plane run only with it)
   // ruleset
   const RuleDesc* rules;
   uint32_t nrules;
@@ -770,6 +772,55 @@ KYV_HD uint8_t expand_meta_root(const View& v, const MetaSite& ms, NodeTab R, co
     }
   }
   return ST_NONE;
+}
+
+// The meta-key plane row of one (class, resource) (kyv_layout.h MetaKeyRow): expand_meta at the class's position, as
+// the walk reaches it (every map on the way type-checked, as the pattern maps above the site do), then the lookup of
+// each resolved key in its labels / annotations map, as the pattern map below the site does. Host (kyv_batch_meta_keys)
+// and device (meta_keys_kernel) run this one function; the compiled walk reads its result instead of redoing it.
+KYV_HD MetaKeyRow meta_key_row(const View& v, const MetaClass& mc, NodeTab R, const ResHeader& h) {
+  const MetaSite& ms = mc.site;
+  const bool two = ms.nwild_l + ms.nwild_a > 1;
+  Keys keys{NONE, NONE};
+  for (uint32_t i = 0; i < ms.nwild_l; i++) keys.set(ms.slot_l + i, v.pool[ms.wild_l + 2 * i + 1]);
+  for (uint32_t i = 0; i < ms.nwild_a; i++) keys.set(ms.slot_a + i, v.pool[ms.wild_a + 2 * i + 1]);
+  uint32_t ent[2] = {NONE, NONE};
+  uint8_t o = ST_NONE;
+  uint32_t rn = h.nnodes ? 0u : NONE;
+  if (rn != NONE && node_type(R[rn]) != N_MAP) rn = NONE;
+  const uint32_t np = mc.pos == 0 ? 0u : mc.pos == 1 ? 2u : 4u;
+  for (uint32_t i = 0; i < np && rn != NONE; i++) {
+    const uint32_t key = i == 1 ? (mc.pos == 1 ? KSID(TEMPLATE) : KSID(JOBTEMPLATE)) : i == 3 ? KSID(TEMPLATE) : KSID(SPEC);
+    rn = map_find(R, rn, key);
+    if (rn != NONE && node_type(R[rn]) != N_MAP) rn = NONE;
+  }
+  if (rn != NONE) {
+    o = expand_meta(v, ms, R, rn, h, keys);
+    const uint32_t meta = o == ST_NONE ? map_find(R, rn, KSID(METADATA)) : NONE;
+    if (meta != NONE && node_type(R[meta]) == N_MAP)
+      for (int tag = 0; tag < 2; tag++) {
+        if (!(tag == 0 ? ms.nwild_l : ms.nwild_a)) continue;
+        const uint32_t lm = map_find(R, meta, tag == 0 ? KSID(LABELS) : KSID(ANNOTATIONS));
+        if (lm == NONE || node_type(R[lm]) != N_MAP) continue;
+        const uint32_t s = tag == 0 ? ms.slot_l : ms.slot_a;
+        ent[s & 1u] = map_find(R, lm, keys.get(s));
+      }
+  }
+  MetaKeyRow row;
+  row.w[0] = ((uint32_t)o << MK_ST_SHIFT) | (keys.k0 & MK_KEY_MASK);
+  if (two) {
+    row.w[1] = keys.k1 & MK_KEY_MASK;
+    for (int s = 0; s < 2; s++)
+      row.w[2 + s] = ent[s] == NONE ? NONE : ((MK_TYPE_UNK << COL_TYPE_SHIFT) | (ent[s] & COL_INDEX_MASK));
+  } else {
+    row.w[1] = NONE; row.w[2] = 0u; row.w[3] = 0u;
+    if (ent[0] != NONE) {
+      const Node& e = R[ent[0]];
+      row.w[1] = (node_type(e) << COL_TYPE_SHIFT) | (ent[0] & COL_INDEX_MASK);
+      row.w[2] = e.a;
+    }
+  }
+  return row;
 }
 
 // MatchPattern (validate.go:31-56) for one compiled pattern; a walk deeper than the stack ends in ST_FALLBACK.

@@ -145,6 +145,12 @@ struct Ruleset {
   // per-wave facts (compiler.cpp assign_wave_facts): all-maps bit j <-> row space fact_spaces[j]; the flattener
   // (Batch::facts) and the generated kernels (jit.cpp) number bits by it
   std::vector<uint32_t> fact_spaces;
+  // meta-key classes (compiler.cpp assign_meta_classes, kyv_layout.h MetaClass): meta_class_of[site] = the class of
+  // metadata site `site` (index into metas) or -1: the site keeps expand_meta. Host, device (the fill kernel reads the
+  // uploaded classes) and generated code number classes by this list.
+  std::vector<MetaClass> meta_classes;
+  std::vector<int8_t> meta_class_of;
+  bool jit_meta_keys = false;       // the generated source reads the meta-key plane (set with jit_tried)
   // runtime-compiled walk kernel (jit.cpp): generated once per ruleset, compiled on first use
   bool jit_tried = false;
   std::vector<uint8_t> jit_rules;   // rule k is walked by the compiled kernel
@@ -237,6 +243,7 @@ struct Results {
   std::vector<int64_t> rule_counts;  // [rule][status] (report summaries)
   double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
   double gmask_ms = 0;  // per-batch device work outside the evaluation: the glob-mask kernel (h2d_ms: the image upload)
+  double meta_keys_ms = 0;  // ... and the meta-key plane's fill kernel (kyv_engine.hip meta_keys_kernel)
   // GPU evaluation split by phase (HIP events on the evaluation stream, averaged over the timed launches):
   // [0] verdict resets + match_kernel(s), [1] compiled condition kernel, [2] pattern walk kernels,
   // [3] failing-path compaction, [4] verdict histogram
@@ -259,13 +266,23 @@ Batch* build_batch(const Ruleset* rs, const char* json, size_t len, const char* 
 void derive_strings(Batch& b, size_t from, int threads);
 void build_path_trie(Ruleset& rs);
 void assign_wave_facts(Ruleset& rs);
+void assign_meta_classes(Ruleset& rs);
+// KYV_META_KEYS=0: the generated source resolves wildcard metadata keys in the walk (expand_meta) as before round 10,
+// and no meta-key plane is filled; read when the source is generated
+bool jit_meta_keys_on();
+// the meta-key plane rows of batch b computed on the host, [class][resource in batch order] (kyv_eval.h meta_key_row)
+std::vector<MetaKeyRow> meta_key_rows_host(const Ruleset& rs, const Batch& b);
+// the device's rows of batch b on `device` (empty: no plane filled there)
+std::vector<MetaKeyRow> meta_key_rows_device(const Batch& b, int device);
+size_t meta_key_plane_bytes(const Batch& b);  // bytes of the batch's plane on one device that filled it (0: none yet)
 // KYV_FACT_MAPS=0: the batch reports "nothing known" (every all-maps bit clear) to the kernels and to
 // kyv_batch_wave_facts; read per evaluation, no recompile
 uint32_t wave_maps_mask();  // AND-ed with a row's all-maps word
 void assign_glob_masks(Ruleset& rs);
 void assign_cond_sets(Ruleset& rs);
+// meta_keys: 1 / 0 = the source reads / does not read the meta-key plane, -1 = as KYV_META_KEYS says now
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond = nullptr,
-                       std::vector<uint16_t>* jit_shape = nullptr);
+                       std::vector<uint16_t>* jit_shape = nullptr, int meta_keys = -1);
 // pattern rules the shape tables can decide (kyv_jit_shapes): a covered RK_PATTERN rule without metadata expansion,
 // preconditions or a fused walk (its match program runs in the match phase)
 bool jit_shape_eligible(const Ruleset& rs, uint32_t k);

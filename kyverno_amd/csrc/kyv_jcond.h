@@ -28,6 +28,13 @@ __device__ __forceinline__ uint64_t jc_col(const View& v, uint32_t col, uint32_t
   const uint32_t off = sld32(v.col_off + col);
   return gcol(v.colv, off, row);
 }
+// the meta-key plane row of (class, resource row) (kyv_layout.h MetaKeyRow): one 16-byte load per lane, a wave's 64
+// rows whole lines; issued with the root scope's column loads (jit.cpp Gen::preload)
+__device__ __forceinline__ kyv_u32x4 jc_meta(const View& v, uint32_t cls, uint32_t row) {
+  if (row == NONE) return kyv_u32x4{0u, NONE, NONE, NONE};  // no override, no entry (either row form)
+  KYV_ACCT_ADD(0, 16);
+  return *(const KYV_AS_GLOBAL kyv_u32x4*)(v.meta_rows + ((size_t)cls * v.nres + row));
+}
 __device__ __forceinline__ uint32_t jc_dec(uint64_t x, uint32_t* t, uint32_t* a) {
   const uint32_t lo = (uint32_t)x;
   *a = (uint32_t)(x >> 32);

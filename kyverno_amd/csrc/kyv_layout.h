@@ -289,6 +289,33 @@ struct MetaSite {       // metadata-expansion site (wildcards.go:62-83)
   uint32_t slot_l, slot_a;   // first slot ids
 };
 
+// Meta-key classes (round 10, compiler.cpp assign_meta_classes): the distinct wildcard metadata sites of compiled
+// pattern rules at one of the three static positions the flattener knows -- 0 the resource root, 1 spec.template,
+// 2 spec.jobTemplate.spec.template. Which key of a resource's labels / annotations a site's glob resolves to is a
+// function of the batch image and the class, so it is computed once per (batch, device) into the meta-key plane
+// (kyv_eval.h meta_key_row, kyv_engine.hip meta_keys_kernel) instead of by every evaluation's walk.
+constexpr uint32_t MAX_META_CLASSES = 8;
+struct MetaClass {
+  uint32_t pos;         // static position of the site's map
+  MetaSite site;        // slot_l / slot_a: 0.. in tag order (the class's own numbering, not a rule's)
+};
+// One plane row per (class, resource), rows of a class in batch order: row (class * nres + resource).
+//   w[0]  bits 28..31: the status override expand_meta returns (ST_NONE / ST_PANIC / ST_FALLBACK / ST_ND);
+//         bits 0..27: the key slot of the class's first wildcard as expand_meta leaves it: the sid of the one key the
+//         glob matched, or ("unresolved") the sid of the pattern key itself (key sids fit 28 bits: Node::tk)
+//   one wildcard:   w[1] = the entry of that key in the labels / annotations map, as a path-column entry's low word
+//                   (type << COL_TYPE_SHIFT | node index; NONE: no such entry, or an override), w[2] = the entry
+//                   node's `a` (its string id), w[3] = 0
+//   two wildcards:  w[1] = the second wildcard's key slot; w[2], w[3] = the two entries' node indices with type
+//                   MK_TYPE_UNK (the leaf reads the value's row), NONE: no entry
+// A resource without a map at the class's position gets the unresolved keys and no entries (the walk does not reach
+// the site there).
+struct MetaKeyRow {
+  uint32_t w[4];
+};
+static_assert(sizeof(MetaKeyRow) == 16, "meta-key row size");
+constexpr uint32_t MK_KEY_MASK = 0x0FFFFFFFu, MK_ST_SHIFT = 28, MK_TYPE_UNK = 0xEu;  // MK_TYPE_UNK == T_UNK (kyv_wave.h)
+
 // well-known strings, seeded right after the fixed sids in every dictionary (K_x sid = SID_FIRST_FREE + x)
 #define KYV_WELL_KNOWN(X)                                                                                    \
   X(METADATA, "metadata") X(LABELS, "labels") X(ANNOTATIONS, "annotations") X(SPEC, "spec")                 \

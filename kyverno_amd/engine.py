@@ -143,6 +143,23 @@ class Batch:
         return dict(json.loads(bits.value.decode()), facts=facts, hot=hot, order=order, shape_keys=keys,
                     shape_paths=shape["paths"], shape_bits=shape["bits"], shape_ordered=shape["ordered"])
 
+    def meta_keys(self, device=None):
+        """The batch's meta-key plane (kyv_batch_meta_keys): what each wildcard metadata site class of the ruleset
+        resolves to for every resource -- `rows` uint32 [classes, n, 4] (resources in batch order, see `wave_facts`
+        `order`), `classes` (position and globs of each class) and `decoded` [classes][n] dicts of `st` (override),
+        `keys` and `values` (texts). device=None: computed on the host; an index: read back from that device, which
+        filled its plane before an evaluation of this batch took the compiled walk."""
+        L = K.lib()
+        dev = -1 if device is None else int(device)
+        o = K.MetaKeysOut()
+        K.check(L.kyv_batch_meta_keys(self.h, dev, ctypes.byref(o)))
+        rows = np.zeros((o.classes, self.n, 4), dtype=np.uint32)
+        desc = ctypes.create_string_buffer(o.desc_len + 1)
+        o = K.MetaKeysOut(rows.ctypes.data, rows.size, ctypes.addressof(desc), o.desc_len + 1, 0, 0)
+        K.check(L.kyv_batch_meta_keys(self.h, dev, ctypes.byref(o)))
+        d = json.loads(desc.value.decode())
+        return {"rows": rows, "classes": d["classes"], "decoded": d["rows"]}
+
     def __del__(self):
         if getattr(self, "h", None):
             K.lib().kyv_batch_free(self.h)
@@ -158,6 +175,8 @@ class Results:
         # per-batch device work before the batch's first evaluation: image upload and glob-mask kernel (ms)
         self.upload_ms = L.kyv_results_batch_ms(h, 0)
         self.gmask_ms = L.kyv_results_batch_ms(h, 1)
+        # ... and the meta-key plane's fill kernel (0 unless this batch's compiled walk reads the plane)
+        self.meta_keys_ms = L.kyv_results_batch_ms(h, 2)
         ph = (ctypes.c_double * 5)()
         L.kyv_results_phase_ms(h, ph, 5)
         # match (incl. verdict resets), cond (compiled condition kernel), walk, compact, hist -- ms per launch
