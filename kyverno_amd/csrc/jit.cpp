@@ -40,6 +40,11 @@ bool jit_meta_keys_on() {
   return !e || atoi(e) != 0;
 }
 
+int jit_jc_chains_mode() {
+  const char* e = getenv("KYV_JC_PRELOAD");
+  return e ? (atoi(e) != 0) : jit_meta_keys_on() ? 1 : 0;
+}
+
 namespace {
 
 struct Gen {
@@ -646,7 +651,7 @@ struct CondGen {
   uint32_t cur_etpos = NONE;  // element trie position of the program being generated (stream_cond)
   std::unordered_map<uint64_t, std::string> progs;  // (program, element trie position) -> function name
 
-  explicit CondGen(const Ruleset& r) : rs(r) {}
+  CondGen(const Ruleset& r, int mode) : rs(r), chains(mode < 0 ? jit_jc_chains_mode() != 0 : mode != 0) {}
   static std::string u(uint32_t x) { return std::to_string(x) + "u"; }
   std::string fresh(const char* p) { return std::string(p) + std::to_string(uid++); }
 
@@ -664,7 +669,30 @@ struct CondGen {
     std::string i, t, a, row;
     uint32_t tpos;
     bool key;   // a map key (JMES_KEYBIT element)
+    // a static field chain not yet read (chains, below): (i, t, a) is the value the chain starts at, lz its keys,
+    // tpos the trie position of its last step
+    std::vector<uint32_t> lz;
   };
+  // Chains (KYV_JC_PRELOAD, read per generated source; on by default): a chain of fields whose steps all have columns
+  // reads the entry of its last step alone -- the entry exists iff the whole chain resolves (kyv_jcond.h jc_field),
+  // so the steps before it decide nothing. field() only lengthens the chain; force() emits the one load where
+  // something other than a field reads the value. The walk by node index for a row that is NONE at run time is one
+  // cold block per chain, from the value the chain starts at. 0: every step reads its own entry, the source of the
+  // commit before, byte for byte; it is also the default under KYV_META_KEYS=0, which stands for the source of before
+  // round 10 (jit_jc_chains_mode).
+  const bool chains;
+  V force(const V& x) {
+    if (x.lz.empty()) return x;
+    V y{fresh("vi"), fresh("vt"), fresh("va"), x.row, x.tpos, false, {}};
+    out << "  uint32_t " << y.i << ", " << y.t << ", " << y.a << ";\n"
+        << "  if (" << x.row << " != NONE) jc_field_e(jc_col(v, " << u(tcol(x.tpos)) << ", " << x.row << "), &" << y.i << ", &"
+        << y.t << ", &" << y.a << ");\n"
+        << "  else {\n    " << y.i << " = " << x.i << ";\n";
+    for (uint32_t key : x.lz)
+      out << "    jc_field(v, R, " << y.i << ", NONE, NONE, " << u(key) << ", &" << y.i << ", &" << y.t << ", &" << y.a << ");\n";
+    out << "  }\n";
+    return y;
+  }
   // declare a fresh value
   V decl(const std::string& i, const std::string& t, const std::string& a, const std::string& row, uint32_t tpos,
          bool key) {
@@ -673,8 +701,15 @@ struct CondGen {
         << " = " << row << ";\n";
     return x;
   }
-  V field(const V& x, uint32_t key) {
-    if (x.key) return decl("NONE", "T_UNK", "0u", "NONE", NONE, false);
+  V field(const V& x0, uint32_t key) {
+    if (x0.key) return decl("NONE", "T_UNK", "0u", "NONE", NONE, false);
+    if (chains && tcol(tchild(x0.tpos, key)) != NONE) {  // a step with a column: the chain grows, nothing is read
+      V y = x0;
+      y.tpos = tchild(x0.tpos, key);
+      y.lz.push_back(key);
+      return y;
+    }
+    const V x = force(x0);
     const uint32_t ct = tchild(x.tpos, key), col = tcol(ct);
     V y{fresh("vi"), fresh("vt"), fresh("va"), fresh("vr"), col == NONE ? NONE : ct, false};
     out << "  uint32_t " << y.i << ", " << y.t << ", " << y.a << ";\n"
@@ -740,8 +775,9 @@ struct CondGen {
     else if (proj) out << "  if (" << x.i << " != NONE) { if (!jc_push(L, ln, " << e << ")) return JS_FB; }\n";
     else out << "  if (!jc_push(L, ln, " << x.i << " == NONE ? NONE : " << e << ")) return JS_FB;\n";
   }
-  void jgen(uint32_t pos, const V& x, bool list, bool proj, int guard) {
+  void jgen(uint32_t pos, const V& x0, bool list, bool proj, int guard) {
     if (!ok || guard > 64) { ok = false; return; }
+    const V x = pos < PEND && P[pos] == JO_FIELD ? x0 : force(x0);  // a chain ends where something else reads it
     if (pos >= PEND) { jend(x, list, proj); return; }
     const uint32_t op = P[pos];
     switch (op) {
@@ -1201,8 +1237,9 @@ struct CondGen {
     out << "  }\n";
     close_loop();
   }
-  void fgen(uint32_t pos, const V& x, bool list, bool proj, int guard) {
+  void fgen(uint32_t pos, const V& x0, bool list, bool proj, int guard) {
     if (!ok || guard > 64) { ok = false; return; }
+    const V x = pos < PEND && P[pos] == JO_FIELD ? x0 : force(x0);
     if (pos >= PEND) { fend(x, list, proj); return; }
     const uint32_t op = P[pos];
     switch (op) {
@@ -1433,7 +1470,7 @@ static std::string meta_signature(const Ruleset& rs, const RuleDesc& rd) {
 }
 
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond,
-                       std::vector<uint16_t>* jit_shape, int meta_keys) {
+                       std::vector<uint16_t>* jit_shape, int meta_keys, int jc_chains) {
   Gen g(rs, meta_keys);
   jit_rules->assign(rs.rules.size(), 0);
   if (jit_shape) jit_shape->assign(rs.rules.size(), 0);
@@ -1444,7 +1481,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   const size_t cap = getenv("KYV_JIT_MAX_RULES") ? (size_t)atol(getenv("KYV_JIT_MAX_RULES")) : 1024;
   // compiled condition rules: deny / foreach rules with JMESPath operands (the rest of the interpreted
   // match_kernel<true>'s rules); KYV_JIT_COND=0 leaves them all on the interpreter
-  CondGen cg(rs);
+  CondGen cg(rs, jc_chains);
   std::vector<uint32_t> crules;
   const bool cond_on = !getenv("KYV_JIT_COND") || atoi(getenv("KYV_JIT_COND")) != 0;
   for (size_t k = 0; k < rs.rules.size() && cond_on && crules.size() < cap; k++) {

@@ -954,7 +954,8 @@ static bool ensure_jit(Ruleset& rs, DevRuleset* dr) {
     rs.jit_tried = true;
     try {
       rs.jit_meta_keys = jit_meta_keys_on() && !rs.meta_classes.empty();
-      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape, rs.jit_meta_keys ? 1 : 0);
+      rs.jit_jc_chains = jit_jc_chains_mode();
+      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains);
       rs.jit_nshapes = 0;
       for (auto x : rs.jit_shape) rs.jit_nshapes = std::max<uint32_t>(rs.jit_nshapes, x);
       bool any = false;
@@ -1026,8 +1027,9 @@ static bool ensure_jit_acct(Ruleset& rs, DevRuleset* dr) {
   std::lock_guard<std::mutex> lk(g_jit_mu);
   if (rs.jit_code_acct.empty()) {
     std::vector<uint8_t> jr, jc;
-    // (the switch as the product source had it: the accounting kernels read the plane exactly when it is filled)
-    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc, nullptr, rs.jit_meta_keys ? 1 : 0), nullptr, true);
+    // (the switches as the product source had them: the accounting kernels read the plane exactly when it is filled,
+    // and count the condition kernels' loads as the product kernels issue them)
+    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc, nullptr, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains), nullptr, true);
   }
   HIP_OK(hipModuleLoadData(&dr->amod, rs.jit_code_acct.data()));
   dr->afns.resize(dr->jfns.size());

@@ -151,6 +151,7 @@ struct Ruleset {
   std::vector<MetaClass> meta_classes;
   std::vector<int8_t> meta_class_of;
   bool jit_meta_keys = false;       // the generated source reads the meta-key plane (set with jit_tried)
+  int jit_jc_chains = 0;           // the condition rules' field chains read their last step alone (set with jit_tried)
   // runtime-compiled walk kernel (jit.cpp): generated once per ruleset, compiled on first use
   bool jit_tried = false;
   std::vector<uint8_t> jit_rules;   // rule k is walked by the compiled kernel
@@ -280,9 +281,15 @@ size_t meta_key_plane_bytes(const Batch& b);  // bytes of the batch's plane on o
 uint32_t wave_maps_mask();  // AND-ed with a row's all-maps word
 void assign_glob_masks(Ruleset& rs);
 void assign_cond_sets(Ruleset& rs);
-// meta_keys: 1 / 0 = the source reads / does not read the meta-key plane, -1 = as KYV_META_KEYS says now
+// KYV_JC_PRELOAD: the compiled condition rules read the last step of a static field chain alone (jit.cpp CondGen
+// chains; 1 by default, 0 under KYV_META_KEYS=0, which stands for the source of before the plane); read when the source
+// is generated
+int jit_jc_chains_mode();
+// meta_keys: 1 / 0 = the source reads / does not read the meta-key plane, -1 = as KYV_META_KEYS says now;
+// jc_chains: 1 / 0 = the condition rules' field chains read / do not read their last step alone, -1 = as
+// KYV_JC_PRELOAD says now
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond = nullptr,
-                       std::vector<uint16_t>* jit_shape = nullptr, int meta_keys = -1);
+                       std::vector<uint16_t>* jit_shape = nullptr, int meta_keys = -1, int jc_chains = -1);
 // pattern rules the shape tables can decide (kyv_jit_shapes): a covered RK_PATTERN rule without metadata expansion,
 // preconditions or a fused walk (its match program runs in the match phase)
 bool jit_shape_eligible(const Ruleset& rs, uint32_t k);

@@ -73,6 +73,13 @@ __device__ __forceinline__ void jc_field(const View& v, const Node* R, uint32_t 
   *ot = node_type(n);
   *oa = n.a;
 }
+// jc_field through a column whose entry is already loaded, at the last step of a static chain of fields (jit.cpp
+// CondGen::force): the entry exists iff the whole chain resolves, so the steps before it are not read
+__device__ __forceinline__ void jc_field_e(uint64_t e, uint32_t* oi, uint32_t* ot, uint32_t* oa) {
+  uint32_t x = jc_dec(e, ot, oa);
+  if (x != NONE && *ot == N_NULL) { x = NONE; *ot = T_UNK; *oa = 0; }
+  *oi = x;
+}
 // array view of a value: element count, first element, row of element 0 in the elements' row space (NONE when the
 // elements have no rows); false when the value is not an array. lencol: the (count, element-0 row) column of the
 // value's trie position, read when the value came through a column
