@@ -399,6 +399,7 @@ struct DeviceResults {
   uint16_t* rcnt = nullptr;
   uint32_t* tsum = nullptr;      // compaction tile sums / offsets
   uint32_t* tseg = nullptr;      // their segment totals / offsets (compact_scan_kernel)
+  uint32_t* ttot = nullptr;      // the tile totals kept beside the offsets (compact_sum_wide_kernel; inside tsum)
   unsigned long long* counts = nullptr;
   size_t max_recs = 0;             // staging slots of the largest slice (d.stage)
   size_t recs_cap = 0;             // records d.recs holds (>= max_recs; grown between slices when a rule-sliced
@@ -779,6 +780,149 @@ __global__ void __launch_bounds__(WAVE) compact_copy_kernel(const FailRec* __res
   }
 }
 
+// Round 12: the same compaction with fewer launches and more loads in flight (KYV_RESULT_KERNELS bit 0; the
+// kernels above stay for A/B and launch with the bit cleared). The tile prefix (compact_scan / compact_top) is shared.
+//   compact_sum_wide_kernel  256-thread blocks, 16-byte loads of the chunk counts: 8 lanes add one tile; the tile's
+//                            total goes to tsum (scanned in place next) and to ttot (kept for the copy);
+//   compact_copy_wide_kernel a grid sized from the CU count; every wave strides over the tiles, reads 64 tile totals
+//                            with one load and visits only the tiles that hold records (an empty tile costs 4 bytes
+//                            read by a lane that is already running). Per tile the chunk counts, the rule fields and
+//                            the output base are loaded together; the (rule, first match wave) of the tile is computed
+//                            once per tile; every lane then copies U records per trip: U searches, U independent
+//                            16-byte loads, then the stores.
+// No workgroup waits for another and no atomic decides a record's place: the order is the scan's.
+constexpr int CSUM_BLOCK = 256;
+__global__ void __launch_bounds__(CSUM_BLOCK) compact_sum_wide_kernel(const uint16_t* __restrict__ rcnt, size_t total,
+                                                                      uint32_t ntiles, uint32_t* __restrict__ tsum,
+                                                                      uint32_t* __restrict__ ttot) {
+  const size_t g = (size_t)blockIdx.x * CSUM_BLOCK + threadIdx.x;  // a group of 8 chunks, 8 groups per tile
+  const size_t c = g * 8;
+  uint32_t n = 0;
+  if (c + 8 <= total) {
+    const kyv_u32x4 q = *(const kyv_u32x4*)(rcnt + c);  // (the counts start 256-byte aligned, c is a multiple of 8)
+    n = (q.x & 0xFFFFu) + (q.x >> 16) + (q.y & 0xFFFFu) + (q.y >> 16) + (q.z & 0xFFFFu) + (q.z >> 16) + (q.w & 0xFFFFu) +
+        (q.w >> 16);
+  } else {
+    for (size_t j = c; j < total; j++) n += rcnt[j];
+  }
+  n += __shfl_xor(n, 1);
+  n += __shfl_xor(n, 2);
+  n += __shfl_xor(n, 4);
+  const size_t t = g >> 3;
+  if ((threadIdx.x & 7) == 0 && t < ntiles) {
+    tsum[t] = n;
+    ttot[t] = n;
+  }
+}
+struct alignas(16) CopySrc {  // what the copy keeps per chunk of the tile in LDS, one 16-byte read per record
+  size_t off16;  // the chunk's staging slots, in 16-byte units from the staging base
+  uint32_t kw;         // global rule | wide << 31 (whole FailRecs staged)
+  uint32_t w;          // match wave
+};
+template <int U>
+__global__ void __launch_bounds__(WAVE) compact_copy_wide_kernel(const FailRec* __restrict__ stage, const uint32_t* __restrict__ rbase,
+                                                                 const uint16_t* __restrict__ rcnt, const RuleDesc* __restrict__ rules,
+                                                                 uint32_t nwaves, size_t total, uint32_t ntiles,
+                                                                 const uint32_t* __restrict__ ttot, const uint32_t* __restrict__ tbase,
+                                                                 const uint32_t* __restrict__ seg, FailRec* __restrict__ out,
+                                                                 size_t max_out, uint32_t k0, const uint32_t* __restrict__ nout) {
+  __shared__ uint32_t spre[WAVE];
+  __shared__ CopySrc ssrc[WAVE];
+  const uint32_t lane = threadIdx.x;
+  const size_t obase = nout[1];
+  const kyv_u32x4* __restrict__ stage16 = reinterpret_cast<const kyv_u32x4*>(stage);
+  for (size_t r0 = blockIdx.x; r0 < ntiles; r0 += (size_t)gridDim.x * WAVE) {
+    // this round's 64 tiles of the wave: r0, r0 + grid, ...: one total per lane, then the tiles that hold records
+    const size_t mine = r0 + (size_t)lane * gridDim.x;
+    const uint32_t tt = mine < ntiles ? ttot[mine] : 0u;
+    unsigned long long live = __ballot(tt != 0);
+    while (live) {
+      const uint32_t bit = (uint32_t)__builtin_ctzll(live);
+      live &= live - 1;
+      const uint32_t t = (uint32_t)(r0 + (size_t)bit * gridDim.x);  // wave-uniform
+      const size_t c0 = (size_t)t * WAVE;
+      // the lanes past the last chunk (the last tile only) read the last chunk's fields and count nothing, so the
+      // tile's set-up has no branch and every load of it is issued before anything waits: counts, rule fields, base
+      const uint32_t last = (uint32_t)min((size_t)WAVE, total - c0) - 1u;
+      const uint32_t le = min(lane, last);
+      const uint32_t kt = total <= 0xFFFFFFFFull ? (uint32_t)c0 / nwaves : (uint32_t)(c0 / nwaves);  // once per tile
+      const uint32_t x = (uint32_t)(c0 - (size_t)kt * nwaves) + le;
+      // 64 consecutive chunks span two rules at most when a rule has 64 waves or more: one wrap test
+      const uint32_t dk = nwaves >= (uint32_t)WAVE ? (x >= nwaves ? 1u : 0u) : x / nwaves;
+      const uint32_t k = kt + dk, w = x - dk * nwaves;
+      const uint32_t nraw = rcnt[c0 + le];
+      const uint32_t kind = rules[k].kind, nalts = rules[k].nalts, wide = rules[k].uses_meta, rb = rbase[k];
+      const size_t base = obase + tbase[t] + seg[t / SCAN_SEG];
+      const uint32_t n = lane <= last ? nraw : 0u;
+      uint32_t pre = n;  // inclusive wave prefix
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const uint32_t y = __shfl_up(pre, off);
+        if ((int)lane >= off) pre += y;
+      }
+      const uint32_t T = __shfl(pre, WAVE - 1);
+      const uint32_t alts = kind == RK_PATTERN ? 1u : min(nalts, (uint32_t)MAX_ALTS);
+      spre[lane] = pre;
+      ssrc[lane] = CopySrc{((size_t)rb + (size_t)w * WAVE * alts) * 2, (k + k0) | (wide ? 0x80000000u : 0u), w};
+      __syncthreads();  // (one wave: a wait for the LDS writes, no barrier)
+      for (uint32_t i0 = 0; i0 < T; i0 += WAVE * U) {
+        uint32_t i[U], j[U], first[U];
+        bool on[U];
+        CopySrc s[U];
+        kyv_u32x4 a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          i[u] = i0 + u * WAVE + lane;
+          on[u] = i[u] < T && base + i[u] < max_out;
+          j[u] = 0;
+        }
+        // U searches side by side: the chunk of record i is the number of inclusive prefixes <= i (a lane past T
+        // ends at chunk 63 and copies nothing)
+#pragma unroll
+        for (uint32_t step = WAVE / 2; step; step >>= 1) {
+          uint32_t v[U];
+#pragma unroll
+          for (int u = 0; u < U; u++) v[u] = spre[j[u] + step - 1];
+#pragma unroll
+          for (int u = 0; u < U; u++) j[u] += v[u] <= i[u] ? step : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          first[u] = j[u] ? spre[j[u] - 1] : 0u;
+          s[u] = ssrc[j[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {  // U independent gathers (a wide record's second half with the first)
+          const bool wd = s[u].kw & 0x80000000u;
+          const kyv_u32x4* p = stage16 + s[u].off16 + (size_t)(i[u] - first[u]) * (wd ? 2 : 1);
+          a[u] = on[u] ? p[0] : kyv_u32x4{0, 0, 0, 0};
+          b[u] = on[u] && wd ? p[1] : kyv_u32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {  // whole FailRecs of wide chunks copied, StageRecs expanded
+          if (!on[u]) continue;
+          kyv_u32x4* dst = reinterpret_cast<kyv_u32x4*>(out + base + i[u]);
+          if (s[u].kw & 0x80000000u) {
+            dst[0] = a[u];
+            dst[1] = b[u];
+          } else {
+            const kyv_u32x4 q = a[u];  // StageRec: tmpl, lane_alt, idx[4]
+            dst[0] = kyv_u32x4{s[u].w * WAVE + (q.y & (WAVE - 1)), s[u].kw, q.x, (q.y >> 8) & 0xFFFFu};  // res, rule, tmpl, alt | nalt 0
+            dst[1] = kyv_u32x4{q.z, q.w, NONE, NONE};                                                      // idx[4], key[2]
+          }
+        }
+      }
+      __syncthreads();  // the next tile overwrites the LDS tables
+    }
+  }
+}
+constexpr int COPY_U = 4;  // records per lane and trip of the wide copy
+template <int U>
+static int copy_wide_per_cu() {  // resident one-wave workgroups per CU (32 when the registers allow 8 waves per SIMD)
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, compact_copy_wide_kernel<U>, WAVE, 0) != hipSuccess || nb < 1) nb = 16;
+  return std::min(nb, 32);
+}
+
 // Verdict totals: one histogram pass over the [rule][res] status bytes after both phases (the verdict bytes are
 // complete there: ST_NONE preset, every decided pair written once). Statuses are 0..7, so a 32-bit word holds four
 // 3-bit values and the bytes equal to s are the zero bytes of word ^ (s * 0x01010101). Per thread u32 tallies,
@@ -788,22 +932,11 @@ __device__ __forceinline__ uint32_t bytes_eq(uint32_t w, uint32_t s) {
   const uint32_t x = w ^ (s * 0x01010101u);
   return 4u - (uint32_t)__popc((x | (x >> 1) | (x >> 2)) & 0x01010101u);
 }
-__global__ void __launch_bounds__(HIST_BLOCK) status_hist_kernel(const uint8_t* __restrict__ status, size_t nres,
-                                                                 unsigned long long* __restrict__ counts) {
-  // blockIdx.y = rule: its verdict row is status[k * nres, (k + 1) * nres); per-rule totals feed the report
-  // summaries (CalculateSummary, pkg/utils/report/results.go:38-54), their sum the evaluation's verdict counts
+// the end of a histogram block: the unaligned head / tail bytes of the row (block 0), wave and block reduction, one
+// atomic per block and status
+__device__ __forceinline__ void hist_finish(uint32_t (&c)[NSTATUS], const uint8_t* __restrict__ row, size_t nres, size_t head,
+                                            size_t tail0, unsigned long long* __restrict__ counts) {
   __shared__ uint32_t part[HIST_BLOCK / WAVE][NSTATUS];
-  uint32_t c[NSTATUS] = {0};
-  const uint8_t* row = status + (size_t)blockIdx.y * nres;
-  size_t head = (16 - ((size_t)row & 15)) & 15;
-  if (head > nres) head = nres;
-  const size_t nv = (nres - head) / 16, tail0 = head + nv * 16, stride = (size_t)gridDim.x * HIST_BLOCK;
-  const kyv_u32x4* s4 = (const kyv_u32x4*)(row + head);
-  for (size_t i = (size_t)blockIdx.x * HIST_BLOCK + threadIdx.x; i < nv; i += stride) {
-    const kyv_u32x4 q = __builtin_nontemporal_load(s4 + i);
-#pragma unroll
-    for (uint32_t s = 1; s < NSTATUS; s++) c[s] += bytes_eq(q.x, s) + bytes_eq(q.y, s) + bytes_eq(q.z, s) + bytes_eq(q.w, s);
-  }
   if (blockIdx.x == 0 && threadIdx.x < head + (nres - tail0)) {  // unaligned head / tail bytes (< 32)
     const size_t at = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
     const uint32_t b = row[at] & 7u;
@@ -825,6 +958,67 @@ __global__ void __launch_bounds__(HIST_BLOCK) status_hist_kernel(const uint8_t* 
     for (int j = 0; j < HIST_BLOCK / WAVE; j++) t += part[j][threadIdx.x];
     if (t) atomicAdd(&counts[(size_t)blockIdx.y * NSTATUS + threadIdx.x], (unsigned long long)t);
   }
+}
+__global__ void __launch_bounds__(HIST_BLOCK) status_hist_kernel(const uint8_t* __restrict__ status, size_t nres,
+                                                                 unsigned long long* __restrict__ counts) {
+  // blockIdx.y = rule: its verdict row is status[k * nres, (k + 1) * nres); per-rule totals feed the report
+  // summaries (CalculateSummary, pkg/utils/report/results.go:38-54), their sum the evaluation's verdict counts
+  uint32_t c[NSTATUS] = {0};
+  const uint8_t* row = status + (size_t)blockIdx.y * nres;
+  size_t head = (16 - ((size_t)row & 15)) & 15;
+  if (head > nres) head = nres;
+  const size_t nv = (nres - head) / 16, tail0 = head + nv * 16, stride = (size_t)gridDim.x * HIST_BLOCK;
+  const kyv_u32x4* s4 = (const kyv_u32x4*)(row + head);
+  for (size_t i = (size_t)blockIdx.x * HIST_BLOCK + threadIdx.x; i < nv; i += stride) {
+    const kyv_u32x4 q = __builtin_nontemporal_load(s4 + i);
+#pragma unroll
+    for (uint32_t s = 1; s < NSTATUS; s++) c[s] += bytes_eq(q.x, s) + bytes_eq(q.y, s) + bytes_eq(q.z, s) + bytes_eq(q.w, s);
+  }
+  hist_finish(c, row, nres, head, tail0, counts);
+}
+// Round 12 (KYV_RESULT_KERNELS bit 1): the same pass with about a sixth of the vector instructions (the kernel above
+// issued ~200 per 16-byte load and was bound by issue, not by bandwidth). The three status bits of the 16 bytes are
+// gathered into three bit planes: two words share a byte as 3 + 3 bits, the planes of the two pairs sit one bit
+// apart; a status is then one AND of planes and its bytes one population count, added to 32-bit tallies that
+// cannot overflow (a thread sees fewer than 2^32 bytes). The high five bits of a byte (marks) are masked off first.
+// Two loads are in flight per thread.
+__device__ __forceinline__ void hist_add16(const kyv_u32x4 q, uint32_t (&c)[NSTATUS]) {
+  constexpr uint32_t K7 = 0x07070707u, K9 = 0x09090909u;
+  const uint32_t e = (q.x & K7) | ((q.y & K7) << 3);  // per byte: 0 0 y2 y1 y0 x2 x1 x0
+  const uint32_t f = (q.z & K7) | ((q.w & K7) << 3);  //           0 0 w2 w1 w0 z2 z1 z0
+  // plane p: bit p of the statuses of x, z, y, w at bits 0, 1, 3, 4 of every byte
+  const uint32_t p0 = (e & K9) | ((f & K9) << 1);
+  const uint32_t p1 = ((e >> 1) & K9) | (f & (K9 << 1));
+  const uint32_t p2 = ((e >> 2) & K9) | ((f >> 1) & (K9 << 1));
+  // every status as one three-input function of the planes (a positive plane in each keeps the unused bits out).
+  // Written as plain minterms on purpose: with shared XOR terms (s26 = p1 ^ (p0 & p1), count(s26 ^ (s26 & p2)))
+  // ROCm 7.2's hipcc folded status 2 into a v_bitop3_b32 (table 0xc4) that also counted statuses 3 and 7;
+  // tests/test_gpu_hist_edges.py caught it. The seven tables below read 0x10 0x10 0x20 0x04 0x40 0x40 0x80.
+  c[1] += __popc(p0 & ~p1 & ~p2);
+  c[2] += __popc(~p0 & p1 & ~p2);
+  c[3] += __popc(p0 & p1 & ~p2);
+  c[4] += __popc(~p0 & ~p1 & p2);
+  c[5] += __popc(p0 & ~p1 & p2);
+  c[6] += __popc(~p0 & p1 & p2);
+  c[7] += __popc(p0 & p1 & p2);
+}
+__global__ void __launch_bounds__(HIST_BLOCK) status_hist_planes_kernel(const uint8_t* __restrict__ status, size_t nres,
+                                                                        unsigned long long* __restrict__ counts) {
+  uint32_t c[NSTATUS] = {0};
+  const uint8_t* row = status + (size_t)blockIdx.y * nres;  // as status_hist_kernel
+  size_t head = (16 - ((size_t)row & 15)) & 15;
+  if (head > nres) head = nres;
+  const size_t nv = (nres - head) / 16, tail0 = head + nv * 16, stride = (size_t)gridDim.x * HIST_BLOCK;
+  const kyv_u32x4* s4 = (const kyv_u32x4*)(row + head);
+  size_t i = (size_t)blockIdx.x * HIST_BLOCK + threadIdx.x;
+  for (; i + stride < nv; i += 2 * stride) {
+    const kyv_u32x4 q0 = __builtin_nontemporal_load(s4 + i);
+    const kyv_u32x4 q1 = __builtin_nontemporal_load(s4 + i + stride);
+    hist_add16(q0, c);
+    hist_add16(q1, c);
+  }
+  if (i < nv) hist_add16(__builtin_nontemporal_load(s4 + i), c);
+  hist_finish(c, row, nres, head, tail0, counts);
 }
 
 // wildcard.Match(pattern g, string s) for every dictionary string (one thread each) and masked pattern; then the
@@ -1916,7 +2110,9 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     HIP_OK(dmalloc(&d.recs, d.max_recs * sizeof(FailRec)));
     d.recs_cap = d.max_recs;
     HIP_OK(dmalloc(&d.rcnt, std::max<size_t>(msr * nwv, 1) * 2));
-    HIP_OK(dmalloc(&d.tsum, std::max<size_t>((msr * nwv + WAVE - 1) / WAVE, 1) * 4));
+    const size_t max_tiles = std::max<size_t>((msr * nwv + WAVE - 1) / WAVE, 1);
+    HIP_OK(dmalloc(&d.tsum, max_tiles * 8));  // the tile offsets, then a copy of the tile totals
+    d.ttot = d.tsum + max_tiles;
     HIP_OK(dmalloc(&d.tseg, std::max<size_t>((msr * nwv + WAVE - 1) / WAVE / SCAN_SEG + 1, 1) * 4));
     // walk work lists: one 64-slot list per (slice rule, match wave)
     HIP_OK(dmalloc(&d.wl.items, std::max<size_t>(1, msr * nwv * WAVE) * sizeof(uint2)));
@@ -2038,6 +2234,13 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
   for (auto& sl : d.slices) wconc = wconc || sl.cm.size() > 2;
   wconc = wconc && walk_conc && !acct;
   if (wconc && !d.wstream) stream_get(&d.wstream, &d.wfork, &d.wjoin);
+  // the result passes' kernels (round 12), read per evaluation for A/B: KYV_RESULT_KERNELS bit 0 the wide compaction
+  // kernels (sum and copy), bit 1 the bit-plane histogram; 0 launches round 11's kernels. KYV_COMPACT_GRID:
+  // workgroups of the wide copy (default: as many as stay resident; tests set a few, so that a wave owns many tiles
+  // and takes several rounds of 64 at a small size)
+  const uint32_t result_k = getenv("KYV_RESULT_KERNELS") ? (uint32_t)atoi(getenv("KYV_RESULT_KERNELS")) : 3u;
+  const bool wide_compact = result_k & 1u, planes_hist = result_k & 2u;
+  const uint32_t copy_grid = getenv("KYV_COMPACT_GRID") ? (uint32_t)std::max(1, atoi(getenv("KYV_COMPACT_GRID"))) : 0u;
   for (int it = 0; it < n; it++) {
     const bool collect = copy_back && out && it == n - 1;
     const double sum_before = phase[0] + phase[1] + phase[2] + phase[3];
@@ -2202,7 +2405,11 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
       const size_t nchunks = nsr * (size_t)d.wl.nwaves;
       const uint32_t ntiles = (uint32_t)((nchunks + WAVE - 1) / WAVE);
       const RuleDesc* drules = (const RuleDesc*)(dr->base + dr->o_rules) + sl.k0;
-      hipLaunchKernelGGL(compact_sum_kernel, dim3(ntiles), dim3(WAVE), 0, stream, d.rcnt, nchunks, d.tsum);
+      if (wide_compact)
+        hipLaunchKernelGGL(compact_sum_wide_kernel, dim3((ntiles + CSUM_BLOCK / 8 - 1) / (CSUM_BLOCK / 8)), dim3(CSUM_BLOCK), 0,
+                           stream, d.rcnt, nchunks, ntiles, d.tsum, d.ttot);
+      else
+        hipLaunchKernelGGL(compact_sum_kernel, dim3(ntiles), dim3(WAVE), 0, stream, d.rcnt, nchunks, d.tsum);
       const uint32_t nseg = (ntiles + SCAN_SEG - 1) / SCAN_SEG;
       hipLaunchKernelGGL(compact_scan_kernel, dim3(std::max<uint32_t>(nseg, 1)), dim3(1024), 0, stream, d.tsum, ntiles, d.tseg);
       hipLaunchKernelGGL(compact_top_kernel, dim3(1), dim3(1024), 0, stream, d.tseg, std::max<uint32_t>(nseg, 1), d.nrecs,
@@ -2234,15 +2441,37 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
           appended += d.max_recs;
         }
       }
-      hipLaunchKernelGGL(compact_copy_kernel, dim3(ntiles), dim3(WAVE), 0, stream, d.stage, sl.rbase, d.rcnt, drules,
-                         d.wl.nwaves, nchunks, d.tsum, d.tseg, d.recs, d.recs_cap, sl.k0, (const uint32_t*)d.nrecs);
+      if (wide_compact) {
+        // as many one-wave workgroups as stay resident (the kernel's occupancy, asked once), never more than the tiles.
+        // U = 4 records per lane and trip: measured 0.633 ms per C3 launch against 0.680 (U = 2) and 0.742 (U = 1)
+        static const int per_cu = copy_wide_per_cu<COPY_U>();
+        const uint32_t cgrid = (uint32_t)std::min<size_t>(ntiles, copy_grid ? copy_grid : (size_t)d.cus * per_cu);
+        hipLaunchKernelGGL(compact_copy_wide_kernel<COPY_U>, dim3(cgrid), dim3(WAVE), 0, stream, d.stage, sl.rbase, d.rcnt,
+                           drules, d.wl.nwaves, nchunks, ntiles, d.ttot, d.tsum, d.tseg, d.recs, d.recs_cap, sl.k0,
+                           (const uint32_t*)d.nrecs);
+      } else {
+        hipLaunchKernelGGL(compact_copy_kernel, dim3(ntiles), dim3(WAVE), 0, stream, d.stage, sl.rbase, d.rcnt, drules,
+                           d.wl.nwaves, nchunks, d.tsum, d.tseg, d.recs, d.recs_cap, sl.k0, (const uint32_t*)d.nrecs);
+      }
       HIP_OK(hipGetLastError());
       HIP_OK(hipEventRecord(sl.ev[3], stream));
-      if (acct) {  // compaction: chunk counts (read twice), tile sums, the staged records read, the dense records written
+      if (acct) {
         uint32_t nr = 0;
         HIP_OK(hipMemcpyAsync(&nr, d.nrecs, 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
-        aphase[3] += 4ull * nchunks + 12ull * ntiles + staged + (uint64_t)nr * sizeof(FailRec);
+        if (wide_compact) {
+          // the sum reads every chunk count once (2 B) and writes a tile's total twice; the scan reads and writes the
+          // tile offsets; the copy reads every tile's total and, for the tiles that hold records only, their 64 counts
+          // and their offset; then the staged records read and the dense records written
+          std::vector<uint32_t> tt(ntiles);
+          HIP_OK(hipMemcpy(tt.data(), d.ttot, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
+          uint64_t live = 0;
+          for (uint32_t x : tt) live += x != 0;
+          aphase[3] += 2ull * nchunks + 20ull * ntiles + live * (2ull * WAVE + 4) + staged + (uint64_t)nr * sizeof(FailRec);
+        } else {
+          // chunk counts (read twice), tile sums, the staged records read, the dense records written
+          aphase[3] += 4ull * nchunks + 12ull * ntiles + staged + (uint64_t)nr * sizeof(FailRec);
+        }
       }
       // (no host synchronisation between slices: every slice has its own events, read after the evaluation)
       if (collect && multi) {  // gather this slice's records before the next slice reuses the buffers (offset 0)
@@ -2260,7 +2489,12 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     const uint32_t hgrid = (uint32_t)std::max<size_t>(
         1, std::min<size_t>(((size_t)d.cus * hmul + nrules - 1) / std::max<size_t>(1, nrules), (nres / 16 + HIST_BLOCK - 1) / HIST_BLOCK));
     if (joined) HIP_OK(hipStreamWaitEvent(stream, d.cjoin, 0));  // the histogram reads every verdict row
-    if (nrules && nres) hipLaunchKernelGGL(status_hist_kernel, dim3(hgrid, (uint32_t)nrules), dim3(HIST_BLOCK), 0, stream, d.status, nres, d.counts);
+    if (nrules && nres) {
+      if (planes_hist)
+        hipLaunchKernelGGL(status_hist_planes_kernel, dim3(hgrid, (uint32_t)nrules), dim3(HIST_BLOCK), 0, stream, d.status, nres, d.counts);
+      else
+        hipLaunchKernelGGL(status_hist_kernel, dim3(hgrid, (uint32_t)nrules), dim3(HIST_BLOCK), 0, stream, d.status, nres, d.counts);
+    }
     HIP_OK(hipGetLastError());
     if (acct) aphase[4] += (uint64_t)nres * nrules;  // the histogram reads every verdict byte
     HIP_OK(hipEventRecord(d.e1, stream));
