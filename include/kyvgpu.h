@@ -25,9 +25,14 @@
  * deny, preconditions and foreach-deny run on the device when every variable is a `{{ request.object... }}`,
  * `{{ request.operation }}` or `{{ element... }}` expression of the JMESPath subset the compiler restates
  * (fields, multi-select lists, flatten projections, keys(@), `||` literals; pkg/engine/variables/evaluate.go:21,
- * operator/*.go, validation.go:319-421). Rules that need the reference CPU engine (other JMESPath functions,
- * context entries, foreach patterns, exceptions, image verification) are classified at compile time; their pairs
- * report KYV_ST_FALLBACK and the caller runs engine.Validate for them.
+ * operator/*.go, validation.go:319-421). A pattern / anyPattern leaf that is exactly one
+ * `{{ request.object.<field chain> }}` variable (identifier or "quoted" segments) is substituted per resource on the
+ * device (substitutePatterns, validation.go:760-782): a key missing on the way is the pair's KYV_ST_ERROR
+ * ("variable substitution failed: ..."), a value that is a map, an array or a string with pattern syntax hands the
+ * pair over (KYV_ST_FALLBACK). Rules that need the reference CPU engine (other JMESPath functions, context entries,
+ * pattern variables in a key, inside a longer string or other than a request.object field chain, more than four
+ * distinct pattern variables in one rule, image verification) are classified at compile time, each with its own
+ * reason; their pairs report KYV_ST_FALLBACK and the caller runs engine.Validate for them.
  *
  * Threading: a kyv_ruleset is immutable after compile and may be shared; batches and results are per
  * call. No C++ exception crosses this ABI; failures return a non-zero code and kyv_last_error()
@@ -376,7 +381,8 @@ enum { KYV_TEXT_MESSAGE = 0, KYV_TEXT_PATH = 1 };
 int64_t kyv_results_texts(const kyv_results* r, const kyv_ruleset* rs, const kyv_batch* b, uint32_t rule, uint32_t res0,
                           uint32_t nres, uint32_t status_mask, int32_t what, char* buf, size_t cap, int32_t* lens);
 /* why a KYV_ST_FALLBACK pair needs the reference engine ("" for other statuses): the rule's compile-time reason
- * ("context", "foreach", "exception", "variables", ...) or the run-time site (value / walk outside the device subset);
+ * ("context", "foreach", "exception", "variables: in a pattern key", ...) or the run-time site (value / walk outside
+ * the device subset, e.g. a pattern variable whose value is a map, an array or a string with pattern syntax);
  * returns the full length, -1 on bad arguments */
 int64_t kyv_results_fallback_reason(const kyv_results* r, const kyv_ruleset* rs, const kyv_batch* b, uint32_t res,
                                     uint32_t rule, char* buf, size_t cap);

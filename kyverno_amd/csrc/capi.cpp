@@ -635,6 +635,33 @@ static bool cond_error_text(const Ruleset& rs, const Batch& b, uint32_t res, uin
   return false;
 }
 
+// substitutePatterns error of a pattern / anyPattern rule (validation.go:294-297: ruleError "variable substitution
+// failed"; vars.go:395-399 names the variable and the JSON pointer of its leaf in the pattern document). Rendered
+// when exactly one variable leaf of the rule fails to resolve; with several, Go's map order picks the one reported
+static bool var_error_text(const Ruleset& rs, const Batch& b, uint32_t res, uint32_t rule, std::string* out) {
+  const RuleDesc& d = rs.rules[rule];
+  const RuleMeta& m = rs.meta[rule];
+  if (d.dyn == NONE) return false;
+  const uint32_t n = rs.pool[d.dyn];
+  uint32_t at = d.dyn + 1;
+  std::vector<uint32_t> miss_at(n, NONE);
+  for (uint32_t q = 0; q < n; q++) {
+    const uint32_t nseg = rs.pool[at];
+    std::vector<uint32_t> segs(rs.pool.begin() + at + 2, rs.pool.begin() + at + 2 + nseg);
+    uint32_t node, miss;
+    if (!host_resolve(b, res, segs, &node, &miss)) miss_at[q] = miss;
+    at += 2 + nseg;
+  }
+  const RuleMeta::DynSite* hit = nullptr;
+  size_t nhit = 0;
+  for (auto& s : m.dyn_sites)
+    if (s.slot < n && miss_at[s.slot] != NONE) { hit = &s; nhit++; }
+  if (nhit != 1 || hit->slot >= m.dyn_segs.size() || miss_at[hit->slot] >= m.dyn_segs[hit->slot].size()) return false;
+  *out = "variable substitution failed: failed to resolve " + hit->var + " at path " + hit->path +
+         ": JMESPath query failed: Unknown key \"" + m.dyn_segs[hit->slot][miss_at[hit->slot]] + "\" in path";
+  return true;
+}
+
 // SubstituteAll of a rule message's request.object references (vars.go; validation.go:469 getDenyMessage, :731
 // buildErrorMessage) for the resource at kind-major position `res`: SM_OK with the text in *o; SM_MISSING when a
 // reference does not resolve (a substitution error); SM_NOT_STRING when the whole message is one reference to a
@@ -775,6 +802,8 @@ static bool render_message(kyv_results* r, const Ruleset& rs, const Batch& b, ui
       return *o = "failed to evaluate preconditions: failed to substitute variables in preconditions: " + e, true;
     return false;
   }
+  if (st == ST_ERROR && sb >> 3 == (ST_MARK_VAR >> 3) && (d.kind == RK_PATTERN || d.kind == RK_ANYPATTERN))
+    return var_error_text(rs, b, res, rule, o);
   if (d.kind == RK_DENY) {  // validateDeny (validation.go:437-479)
     if (st == ST_PASS) return *o = "validation rule '" + m.name + "' passed.", true;
     if (st == ST_FAIL) return m.message_vars ? false : deny_message(m, b, res, o);

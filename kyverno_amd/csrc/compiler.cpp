@@ -349,6 +349,9 @@ struct Cx {
   // entry's element variables (kind 0 path / 1 elementIndex, path segments as sids)
   bool dyn_ok = false;
   std::vector<std::vector<uint32_t>> dyn;
+  // compiling a plain pattern / anyPattern: a value that is exactly one `{{ request.object.<field chain> }}` variable
+  // becomes an L_DYN leaf; dyn then holds the rule's variables ([2, nseg, key sids...], collect_pattern_vars)
+  bool dyn_obj = false;
   bool uses_op = false;        // some condition read request.operation
   uint32_t tmpl(const std::string& s) {
     auto it = rs.template_ids.find(s);
@@ -495,6 +498,19 @@ bool keys_have_vars(const Value& p) {
   return false;
 }
 
+bool object_var(const std::string& s, std::vector<std::string>& segs, std::string* text);
+
+// a plain pattern value that is exactly one `{{ request.object(.ident | ."quoted")+ }}` variable -> [2, nseg, sids...]
+bool object_var_desc(Cx& c, const std::string& s, std::vector<uint32_t>* d, std::vector<std::string>* segs_out = nullptr,
+                     std::string* text = nullptr) {
+  std::vector<std::string> segs;
+  if (!object_var(s, segs, text) || segs.empty()) return false;
+  *d = {2u, (uint32_t)segs.size()};
+  for (auto& g : segs) d->push_back(c.sid(g));
+  if (segs_out) *segs_out = segs;
+  return true;
+}
+
 uint32_t compile_leaf(Cx& c, const Value& p) {  // pattern.Validate leaf types
   Leaf L{};
   L.exact = NONE;
@@ -520,6 +536,16 @@ uint32_t compile_leaf(Cx& c, const Value& p) {  // pattern.Validate leaf types
         while (slot < c.dyn.size() && c.dyn[slot] != d) slot++;
         if (slot == c.dyn.size()) c.dyn.push_back(d);
         if (c.dyn.size() > MAX_DYN) throw Fallback{"foreach: more element variables than the device resolves"};
+        L.type = L_DYN;
+        L.exact = slot;
+        break;
+      }
+      if (c.dyn_obj && p.s.find("{{") != std::string::npos) {  // (collect_pattern_vars accepted the document)
+        std::vector<uint32_t> d;
+        if (!object_var_desc(c, p.s, &d)) throw Fallback{"variables: other than a request.object field chain"};
+        uint32_t slot = 0;
+        while (slot < c.dyn.size() && c.dyn[slot] != d) slot++;
+        if (slot == c.dyn.size()) throw Fallback{"variables: a pattern variable outside the rule's variable list"};
         L.type = L_DYN;
         L.exact = slot;
         break;
@@ -2054,12 +2080,58 @@ Value resolve_references(const Value& doc) {
 }
 
 // ---------------------------------------------------------------- rule classification
-bool contains_vars(const Value& v) {  // after reference resolution: `{{ }}` variables remain for the CPU engine
+// The `{{ }}` variables of a pattern / anyPattern document after reference resolution (substitutePatterns,
+// validation.go:760-782: the whole document is substituted before the walk, an anyPattern list at once). The device
+// resolves a leaf that is exactly one `{{ request.object.<field chain> }}` variable (an L_DYN leaf): the rule's
+// distinct variables go to c.dyn (at most MAX_DYN), every variable leaf to `sites` with its JSON pointer in the
+// document (keys as written, '/' escaped as "\/": traverse.go:93). Every other form keeps the rule on the CPU engine,
+// each with its own reason.
+void collect_pattern_vars(Cx& c, const Value& v, const std::string& path, RuleMeta& rm) {
   auto hit = [](const std::string& s) { return s.find("{{") != std::string::npos; };
-  if (v.t == T::Str) return hit(v.s);
-  if (v.t == T::Arr) { for (auto& e : v.a) if (contains_vars(e)) return true; return false; }
-  if (v.t == T::Obj) { for (auto& kv : v.o) if (hit(kv.first) || contains_vars(kv.second)) return true; }
-  return false;
+  if (v.t == T::Str) {
+    if (!hit(v.s)) return;
+    const std::string& s = v.s;
+    const bool whole = s.size() >= 4 && s.compare(0, 2, "{{") == 0 && s.compare(s.size() - 2, 2, "}}") == 0 &&
+                       s.find('{', 2) == std::string::npos && s.find('}') == s.size() - 2;
+    if (!whole) throw Fallback{"variables: embedded in a longer string"};
+    std::vector<std::string> segs;
+    std::string text;
+    if (!object_var(s, segs, &text)) throw Fallback{"variables: other than a request.object field chain"};
+    if (segs.empty()) throw Fallback{"variables: bare request.object"};
+    std::vector<uint32_t> d;
+    object_var_desc(c, s, &d);
+    uint32_t slot = 0;
+    while (slot < c.dyn.size() && c.dyn[slot] != d) slot++;
+    if (slot == c.dyn.size()) {
+      if (c.dyn.size() >= MAX_DYN) throw Fallback{"variables: more distinct variables than the device resolves per rule"};
+      c.dyn.push_back(d);
+      rm.dyn_segs.push_back(segs);
+    }
+    rm.dyn_sites.push_back({slot, text, path});
+    return;
+  }
+  if (v.t == T::Arr) {
+    for (size_t i = 0; i < v.a.size(); i++) collect_pattern_vars(c, v.a[i], path + "/" + std::to_string(i), rm);
+    return;
+  }
+  if (v.t == T::Obj)
+    for (auto& kv : v.o) {
+      if (hit(kv.first)) throw Fallback{"variables: in a pattern key"};
+      collect_pattern_vars(c, kv.second, path + "/" + replace_all(kv.first, "/", "\\/"), rm);
+    }
+}
+
+// the rule's variable list as RuleDesc::dyn (the path columns are filled in by build_path_trie)
+uint32_t emit_rule_dyn(Cx& c) {
+  if (c.dyn.empty()) return NONE;
+  const uint32_t at = (uint32_t)c.rs.pool.size();
+  c.rs.pool.push_back((uint32_t)c.dyn.size());
+  for (auto& d : c.dyn) {
+    c.rs.pool.push_back(d[1]);
+    c.rs.pool.push_back(NONE);
+    c.rs.pool.insert(c.rs.pool.end(), d.begin() + 2, d.end());
+  }
+  return at;
 }
 
 std::string fallback_reason(const Value& r) {  // validator.validate dispatch (validation.go:276-317)
@@ -2068,8 +2140,7 @@ std::string fallback_reason(const Value& r) {  // validator.validate dispatch (v
   if (nonempty(r.get("verifyImages"))) return "verifyImages";
   if (!val) return "";
   if (!nil(val->get("deny"))) return val->get("deny")->t == T::Obj ? "" : "deny";
-  if ((val->get("pattern") && contains_vars(*val->get("pattern"))) || (val->get("anyPattern") && contains_vars(*val->get("anyPattern"))))
-    return "variables";
+  // (variables of a pattern / anyPattern: collect_pattern_vars, when the rule is compiled)
   if (!nil(val->get("manifests"))) return "manifests";
   return "";
 }
@@ -2130,6 +2201,7 @@ Ruleset* compile_ruleset(const char* json, size_t len, std::string* err, const c
         RuleDesc rd{};
         rd.pre = NONE;
         rd.exc = NONE;
+        rd.dyn = NONE;
         RuleMeta rm;
         rm.name = r.str_or("name");
         rm.message = val ? val->str_or("message") : "";
@@ -2195,7 +2267,11 @@ Ruleset* compile_ruleset(const char* json, size_t len, std::string* err, const c
             rm.message_vars = !compile_message(c, rm.message, rm);
           } else if (val && !nil(val->get("pattern"))) {
             rd.kind = RK_PATTERN;
+            collect_pattern_vars(c, *rval->get("pattern"), "", rm);
+            c.dyn_obj = true;
             rd.root = compile_pattern_root(c, *rval->get("pattern"));
+            c.dyn_obj = false;
+            rd.dyn = emit_rule_dyn(c);
             // buildErrorMessage substitutes the message's variables (validation.go:722-745): request.object
             // references are rendered on the host from the resource (capi.cpp subst_message)
             rm.message_vars = !compile_message(c, rm.message, rm);
@@ -2206,7 +2282,11 @@ Ruleset* compile_ruleset(const char* json, size_t len, std::string* err, const c
               rm.reason = "failed to deserialize anyPattern, expected type array";
             } else {
               std::vector<uint32_t> roots;
+              collect_pattern_vars(c, *ap, "", rm);  // (substitution is per rule: one list for all alternatives)
+              c.dyn_obj = true;
               for (auto& p : ap->a) roots.push_back(compile_pattern_root(c, p));
+              c.dyn_obj = false;
+              rd.dyn = emit_rule_dyn(c);
               if (roots.size() > MAX_ALTS) throw Fallback{"too many anyPattern alternatives"};
               rd.kind = RK_ANYPATTERN;
               rd.root = (uint32_t)rs->pool.size();
@@ -2245,6 +2325,10 @@ Ruleset* compile_ruleset(const char* json, size_t len, std::string* err, const c
           rd.kind = RK_FALLBACK;
           rd.pre = NONE;
           rd.exc = NONE;
+          rd.dyn = NONE;
+          c.dyn_obj = false;
+          rm.dyn_sites.clear();
+          rm.dyn_segs.clear();
           rm.exc_keys.clear();
           rm.reason = f.why;
           rm.msg_parts.clear();
@@ -2411,6 +2495,20 @@ struct TrieBuilder {
     uint32_t t = 0;
     for (uint32_t s = 0; s < o.nseg && t != NONE; s++) t = ch(t, rs.pool[o.a + s]);
     o.list = (t == NONE || o.nseg == 0) ? 0u : rs.trie[t].col + 1;
+  }
+  // the `{{ request.object.<path> }}` variables of a pattern rule (RuleDesc::dyn): each whole path is one column of the
+  // resource row space, read once per pair before the walk
+  void dyn_rule(const RuleDesc& rd) {
+    if ((rd.kind != RK_PATTERN && rd.kind != RK_ANYPATTERN) || rd.dyn == NONE) return;
+    const uint32_t n = rs.pool[rd.dyn];
+    uint32_t at = rd.dyn + 1;
+    for (uint32_t q = 0; q < n; q++) {
+      const uint32_t nseg = rs.pool[at];
+      uint32_t t = 0;
+      for (uint32_t s = 0; s < nseg; s++) t = child(t, rs.pool[at + 2 + s]);
+      rs.pool[at + 1] = nseg ? rs.trie[t].col : NONE;
+      at += 2 + nseg;
+    }
   }
   // a chain-form JMESPath operand (kyv_layout.h jmes_chain_form: fields, then `|| lit` and / or one function) whose
   // fields jmes() registered: the column of the field chain (o.list = column + 1), which the light kernels' chain
@@ -2694,6 +2792,7 @@ void build_path_trie(Ruleset& rs) {
       for (uint32_t a = 0; a < rd.nalts; a++) tb.walk(rs.pool[rd.root + a], 0, 0);
   }
   for (auto& rd : rs.rules) tb.cond_rule(rd);
+  for (auto& rd : rs.rules) tb.dyn_rule(rd);
   if (!getenv("KYV_PSS_NOCOLS"))
     for (auto& rd : rs.rules) tb.pss_rule(rd);
   // entries of pnodes that conflicted after their first visit assigned columns: clear the whole subtree

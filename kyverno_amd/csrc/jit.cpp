@@ -223,6 +223,63 @@ struct Gen {
   static std::string u(uint32_t x) { return std::to_string(x) + "u"; }
   static std::string i64(int64_t x) { return "(int64_t)" + std::to_string(x) + "ll"; }
 
+  // `{{ request.object.<path> }}` pattern variables (RuleDesc::dyn, L_DYN leaves). A rule's variables are resolved by
+  // each of its root functions before the walker state exists: the variables' column entries are read in the root
+  // scope's preload round (dyn_preload), decoded straight-line into Val dv[] for a typed entry, and a lane without an
+  // entry walks the keys in the cold block, which ends the pair with the substitution error when a key is missing
+  // (dyn_decode); the leaves compare against w.dyn[slot]. The root pattern node's function names the rule's whole
+  // variable list (cur_sig), so two patterns that differ only in the variables they name are two shapes: they share
+  // neither a root function nor a shape-table entry.
+  uint32_t cur_root = NONE;  // the root being generated and its rule's variable list (NONE: no variables)
+  uint32_t cur_dyn = NONE;
+  std::string dyn_sig(uint32_t dyn) const {
+    std::ostringstream o;
+    const uint32_t n = rs.pool[dyn];
+    uint32_t at = dyn + 1;
+    for (uint32_t q = 0; q < n; q++) {
+      o << (q ? "; " : "") << "column " << rs.pool[at + 1] << " keys";
+      for (uint32_t s = 0; s < rs.pool[at]; s++) o << " " << rs.pool[at + 2 + s];
+      at += 2 + rs.pool[at];
+    }
+    return o.str();
+  }
+  std::string dyn_preload(uint32_t dyn) const {
+    if (dyn == NONE) return std::string();
+    std::ostringstream o;
+    const uint32_t n = std::min(rs.pool[dyn], MAX_DYN);
+    uint32_t at = dyn + 1;
+    o << "  uint64_t dq[" << n << "];";
+    for (uint32_t q = 0; q < n; q++) {
+      o << " dq[" << q << "] = " << (rs.pool[at + 1] == NONE ? std::string("COL_NONE;") : "jc_col(v, " + u(rs.pool[at + 1]) + ", row);");
+      at += 2 + rs.pool[at];
+    }
+    o << "\n";
+    return o.str();
+  }
+  // before the value loop of a variable leaf: a variable whose value is a map or an array is another pattern, whatever
+  // the resource holds (eval_pattern); nothing for a literal leaf
+  std::string dyn_composite(uint32_t lid) const {
+    const Leaf& L = rs.leaves[lid];
+    if (L.type != L_DYN) return std::string();
+    const std::string d = "w.dyn[" + std::to_string(L.exact) + "].t";
+    return "  if (" + d + " == N_MAP || " + d + " == N_ARR) { w.ost = ST_FALLBACK; return ok_ret(); }\n";
+  }
+  std::string dyn_decode(uint32_t dyn) const {
+    if (dyn == NONE) return std::string();
+    std::ostringstream o;
+    const uint32_t n = std::min(rs.pool[dyn], MAX_DYN);
+    uint32_t at = dyn + 1;
+    o << "  Val dv[" << n << "];\n";
+    for (uint32_t q = 0; q < n; q++) {
+      o << "  { uint32_t dt, da; const uint32_t di = jdec(dq[" << q << "], &dt, &da);\n"
+           "    if (di != NONE) dv[" << q << "] = jdyn_value(v, R, di, dt, da);\n"
+           "    else if (!dyn_walk_value(v, NodeTab{R}, v.pool + " << u(at) << ", &dv[" << q << "])) {  // cold: no entry\n"
+           "      out.status = (uint8_t)(ST_ERROR | ST_MARK_VAR); return; } }\n";
+      at += 2 + rs.pool[at];
+    }
+    return o.str();
+  }
+
   // pattern.Validate(value, pattern) for one compiled leaf, as an expression-statement block that sets `okv`
   // (and `fb`) from Val `x`: the type matrix of leaf_match with the pattern constants folded in, and the
   // string mini-language's OR-of-AND atom groups unrolled in evaluation order.
@@ -271,6 +328,7 @@ struct Gen {
         break;
       }
       case L_MAP: o << "okv = x.t == N_MAP;"; break;
+      case L_DYN: o << "okv = leaf_match_dyn(w.v, w.dyn[" << L.exact << "], x, &fb);"; break;
       default: o << "okv = false;";
     }
     return o.str();
@@ -308,12 +366,14 @@ struct Gen {
     const std::string T = u(P.tmpl);
     out << "static __device__ __forceinline__ Ret p" << pn
         << "(JW& w, uint32_t rn, uint32_t rt, uint32_t ra, uint32_t row, const uint64_t* pc) {\n";
+    if (pn == cur_root && cur_dyn != NONE) out << "  // variables (w.dyn): " << dyn_sig(cur_dyn) << "\n";
     switch (P.kind) {
       case P_MAP: map(pn, P); break;
       case P_LEAF:
         // a string / boolean / null whose type and `a` came with the column needs no row read
         out << "  const bool known = rt == N_STR || rt == N_TRUE || rt == N_FALSE || rt == N_NULL;\n"
-               "  bool fb = false, okv = true;\n";
+               "  bool fb = false, okv = true;\n"
+            << dyn_composite(P.first);
         // the common wave: every lane's value is absent or came typed with its column entry. One wave-uniform test
         // takes such a wave through a straight-line compare (no node row, no array-valued-leaf loop); a wave with a
         // number, a map or an array at this leaf in some lane runs the general form below for all its lanes, as before
@@ -341,7 +401,8 @@ struct Gen {
       case P_ARR_SCALAR: {
         uint32_t leaf = rs.pnodes[P.first].first;
         array_head(pn, T);
-        out << "  bool fb = false, okv = true;\n";
+        out << "  bool fb = false, okv = true;\n"
+            << dyn_composite(leaf);
         const uint32_t self = rs.pn_self[pn];
         out << "  for (uint32_t i = 0; i < cnt && okv; i++) {\n";
         if (self != NONE)
@@ -1509,6 +1570,8 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   std::ostringstream body;
   std::unordered_map<std::string, uint32_t> shapes;  // canonical code -> representative root
   std::unordered_map<uint32_t, uint32_t> rep_of;     // root -> representative root
+  std::unordered_map<uint32_t, uint32_t> root_dyn;   // root -> its rule's variable list (RuleDesc::dyn)
+  auto dyn_of = [&](uint32_t r) { auto it = root_dyn.find(r); return it == root_dyn.end() ? NONE : it->second; };
   auto canon = [](const std::string& t) {
     std::unordered_map<std::string, size_t> ids;
     std::string o;
@@ -1528,6 +1591,12 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
       o += t[i++];
     }
     return o;
+  };
+  // the dedup key of a root: its canonical code and, explicitly, its rule's variable list (the root function resolves
+  // that list, so two patterns that differ only in the variables they name must not share one; the list also stands
+  // in the root pattern function's text as a comment, but the key does not rest on it)
+  auto shape_key = [&](const std::string& text, uint32_t dyn) {
+    return dyn == NONE ? canon(text) : canon(text) + "\n#variables: " + g.dyn_sig(dyn);
   };
   size_t nshapes = 0;
   const bool only_cond = getenv("KYV_JIT_ONLY_COND") && atoi(getenv("KYV_JIT_ONLY_COND")) != 0;  // experiments only
@@ -1549,10 +1618,14 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     for (uint32_t r : rr) {
       std::ostringstream t;
       t.swap(g.out);
+      g.cur_root = r;
+      g.cur_dyn = rd.dyn;
+      root_dyn[r] = rd.dyn;
       g.node(r, 0);
+      g.cur_root = g.cur_dyn = NONE;
       t.swap(g.out);
       if (!g.ok) break;
-      std::string c = canon(t.str());
+      std::string c = shape_key(t.str(), rd.dyn);
       auto it = shapes.find(c);
       if (it != shapes.end()) alias.push_back({r, it->second});
       else texts.push_back({r, t.str()});
@@ -1563,7 +1636,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
       continue;
     }
     for (auto& tx : texts) {
-      shapes.emplace(canon(tx.second), tx.first);
+      shapes.emplace(shape_key(tx.second, rd.dyn), tx.first);
       rep_of[tx.first] = tx.first;
       body << tx.second;
       nshapes++;
@@ -1743,9 +1816,11 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
           << "(const View& v, const Node* R, const ResHeader* hp, uint32_t row, uint32_t mbase, bool rootmap, bool walk,\n"
              "    PatOut& out, const uint32_t am) {\n"
              "  " << g.preload(r, "pc", "row", "jc_col(v, ") << "\n"
+          << g.dyn_preload(dyn_of(r)) <<
              "  if (!walk) return;\n"
              "#ifdef KYV_EXP_JIT_PRELOAD\n  { uint64_t x = 0; for (auto q : pc) x ^= q; out.status = x == 0x123456789ull ? ST_FAIL : ST_PASS; return; }\n#endif\n"
-             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am};\n"
+          << g.dyn_decode(dyn_of(r)) <<
+             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n"
              "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
              "  jfinish(w, r, out);\n"
              "}\n";
@@ -1821,8 +1896,10 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
           else src << " pc[" << i << "] = jc_col(v, " << Gen::u(L[i]) << ", row);";
         }
         src << "\n"
+            << g.dyn_preload(dyn_of(r)) <<
                "  if (!walk) return;\n"
-               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am};\n"
+            << g.dyn_decode(dyn_of(r)) <<
+               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n"
                "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
                "  jfinish(w, r, out);\n"
                "}\n";

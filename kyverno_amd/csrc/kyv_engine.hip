@@ -2698,6 +2698,7 @@ std::string fallback_why(const Ruleset& rs, const Batch& b, uint32_t res, uint32
     case FBW_DEPTH: return "pattern walk deeper than the device frame stack";
     case FBW_VALUE: return "value outside the device subset (quantity beyond int128 nano units)";
     case FBW_META: return "anchor-like key under metadata (wildcard expansion)";
+    case FBW_VAR: return "pattern variable's value outside the device subset (a map, an array, or a string with pattern syntax)";
     default: return "pattern walk outside the device subset";
   }
 }
@@ -2760,6 +2761,7 @@ struct TextWalk {
   uint64_t seen = 0, found = 0;
   Keys keys{NONE, NONE};
   bool bad = false;  // a case whose text needs the reference engine
+  const Val* dyn = nullptr;  // the rule's substituted pattern variables (RuleDesc::dyn), L_DYN leaves
   struct Err {
     bool err = false;
     uint8_t code = EC_NONE;  // typed anchor error (anchor/error.go) or EC_NONE: untyped, classified by substring
@@ -2810,6 +2812,19 @@ struct TextWalk {
       case L_BOOL: return L.bval ? "true" : "false";
       case L_FLOAT: return go_float_g(L.f);
       case L_STR: return str(L.exact);
+      case L_DYN: {  // the substituted value (JSON-context numbers are float64)
+        if (!dyn || L.exact >= MAX_DYN) { bad = true; return ""; }
+        const Val& p = dyn[L.exact];
+        switch (p.t) {
+          case N_NULL: return "<nil>";
+          case N_TRUE: return "true";
+          case N_FALSE: return "false";
+          case N_INT: return go_float_g((double)p.i);
+          case N_FLOAT: return go_float_g(p.f);
+          case N_STR: return str(p.sid);
+          default: bad = true; return "";
+        }
+      }
       default: bad = true; return "";
     }
   }
@@ -2824,12 +2839,21 @@ struct TextWalk {
   static Err mk(uint8_t code, std::string t) { Err e; e.err = true; e.code = code; e.text = std::move(t); return e; }
   bool leaf_ok(const Leaf& L, uint32_t rn) {
     bool fb = false;
-    const bool ok = leaf_match(v, L, value_of(v, R, rn), &fb);
+    if (L.type == L_DYN && (!dyn || L.exact >= MAX_DYN || dyn[L.exact].t == N_MAP || dyn[L.exact].t == N_ARR)) {
+      bad = true;
+      return false;
+    }
+    const bool ok = L.type == L_DYN ? leaf_match_dyn(v, dyn[L.exact], value_of(v, R, rn), &fb)
+                                    : leaf_match(v, L, value_of(v, R, rn), &fb);
     if (fb) bad = true;
     return ok;
   }
   Err leaf(const Leaf& L, uint32_t rn, const std::string& path, std::string* rp) {  // validate.go:92-107
     bool ok = true;
+    if (L.type == L_DYN && dyn && L.exact < MAX_DYN && (dyn[L.exact].t == N_MAP || dyn[L.exact].t == N_ARR)) {
+      bad = true;  // a map / array value is another pattern (eval_pattern hands the pair over)
+      return Err{};
+    }
     if (rn != NONE && node_type(R[rn]) == N_ARR) {
       for (uint32_t i = 0; i < R[rn].b && ok; i++) ok = leaf_ok(L, R[rn].a + i);
     } else {
@@ -2977,6 +3001,11 @@ bool pattern_error_text(const Ruleset& rs, const Batch& b, uint32_t res, uint32_
   View v = make_view(rs, b, nullptr, nullptr, nullptr, nullptr);
   const ResHeader& h = b.hdr[res];
   TextWalk w{rs, v, NodeTab{b.nodes.data() + h.root}, h, rs.rules[rule]};
+  Val dyn[MAX_DYN] = {};
+  if (rs.rules[rule].dyn != NONE) {  // substitutePatterns before the walk (a failed substitution: capi.cpp var_error_text)
+    if (!dyn_walk_values(v, w.R, rs.rules[rule].dyn, dyn)) return false;
+    w.dyn = dyn;
+  }
   std::string p;
   TextWalk::Err e = w.elem(0, root, "/", &p);
   if (w.bad) return false;

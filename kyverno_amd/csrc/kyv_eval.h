@@ -84,7 +84,7 @@ KYV_HD void touch_row(uint32_t i) {
 // of the last ST_FALLBACK it produced; the device build compiles the hook away (the reason is recomputed on the host
 // for the pairs a caller asks about).
 enum FallbackWhy : int { FBW_NONE = 0, FBW_MATCH = 1, FBW_PHRASE = 2, FBW_COND = 3, FBW_DEPTH = 4, FBW_VALUE = 5,
-                         FBW_META = 6 };
+                         FBW_META = 6, FBW_VAR = 7 };
 inline thread_local int g_fb_why = FBW_NONE;
 #if defined(__HIP_DEVICE_COMPILE__)
 #define KYV_WHY(c) ((void)0)
@@ -420,6 +420,34 @@ KYV_HD uint32_t map_find(NodeTab R, uint32_t m, uint32_t key) {
     if (k < key) lo = mid + 1; else hi = mid;
   }
   return NONE;
+}
+
+// The value of one `{{ request.object.<path> }}` pattern variable (RuleDesc::dyn; d: nseg, column, key sids) by the key
+// walk from the resource root, as the JSON context's field chain resolves it (kyverno/go-jmespath fork): a key
+// missing from a map is NotFoundError -> false (the rule's substitution fails); a field of null or of a non-map, and a
+// present null, are null
+KYV_HD bool dyn_walk_value(const View& v, NodeTab R, const uint32_t* d, Val* out) {
+  uint32_t cur = 0;
+  for (uint32_t s = 0; s < d[0]; s++) {
+    if (node_type(R[cur]) != N_MAP) { cur = NONE; break; }
+    const uint32_t x = map_find(R, cur, d[2 + s]);
+    if (x == NONE) return false;
+    cur = x;
+  }
+  *out = value_of(v, R, cur);
+  if (out->t == 0xFF) out->t = N_NULL;
+  return true;
+}
+// every variable of a rule (pool offset `dyn`) for one resource, by the key walk; false: some key is missing
+KYV_HD bool dyn_walk_values(const View& v, NodeTab R, uint32_t dyn, Val* out) {
+  const uint32_t n = v.pool[dyn];
+  uint32_t at = dyn + 1;
+  bool ok = true;
+  for (uint32_t q = 0; q < n && q < MAX_DYN; q++) {
+    if (!dyn_walk_value(v, R, v.pool + at, &out[q])) ok = false;
+    at += 2 + v.pool[at];
+  }
+  return ok;
 }
 
 // ---------------------------------------------------------------- match programs
@@ -870,6 +898,9 @@ KYV_FN_PATTERN void eval_pattern(const View& v, uint32_t root, NodeTab R, const 
         bool okv = true;
         const bool dl = L.type == L_DYN;
         if (dl && !dyn) { KYV_WHY(FBW_VALUE); out.status = ST_FALLBACK; return; }
+        // a variable whose value is a map or an array is another pattern (validateMap / validateArray), whatever the
+        // resource holds (an empty resource array would not reach leaf_match_dyn)
+        if (dl && (dyn[L.exact].t == N_MAP || dyn[L.exact].t == N_ARR)) { KYV_WHY(FBW_VAR); out.status = ST_FALLBACK; return; }
         if (rt == N_ARR) {
           const Node& A = R[ern];
           for (uint32_t i = 0; i < A.b && okv; i++)
@@ -877,7 +908,7 @@ KYV_FN_PATTERN void eval_pattern(const View& v, uint32_t root, NodeTab R, const 
         } else {
           okv = dl ? leaf_match_dyn(v, dyn[L.exact], value_of(v, R, ern), &fb) : leaf_match(v, L, value_of(v, R, ern), &fb);
         }
-        if (fb) { KYV_WHY(FBW_VALUE); out.status = ST_FALLBACK; return; }
+        if (fb) { KYV_WHY(dl ? FBW_VAR : FBW_VALUE); out.status = ST_FALLBACK; return; }
         ret = okv ? ok_ret() : mkerr(EC_NONE, 0, P.tmpl);
         action = 2;
         continue;
@@ -891,9 +922,12 @@ KYV_FN_PATTERN void eval_pattern(const View& v, uint32_t root, NodeTab R, const 
         bool okv = true;
         const bool dl = L.type == L_DYN;
         if (dl && !dyn) { KYV_WHY(FBW_VALUE); out.status = ST_FALLBACK; return; }
+        // a variable whose value is a map or an array is another pattern (validateMap / validateArray), whatever the
+        // resource holds (an empty resource array would not reach leaf_match_dyn)
+        if (dl && (dyn[L.exact].t == N_MAP || dyn[L.exact].t == N_ARR)) { KYV_WHY(FBW_VAR); out.status = ST_FALLBACK; return; }
         for (uint32_t i = 0; i < A.b && okv; i++)
           okv = dl ? leaf_match_dyn(v, dyn[L.exact], value_of(v, R, A.a + i), &fb) : leaf_match(v, L, value_of(v, R, A.a + i), &fb);
-        if (fb) { KYV_WHY(FBW_VALUE); out.status = ST_FALLBACK; return; }
+        if (fb) { KYV_WHY(dl ? FBW_VAR : FBW_VALUE); out.status = ST_FALLBACK; return; }
         ret = okv ? ok_ret() : mkerr(EC_NONE, 0, P.tmpl);
         action = 2;
         continue;

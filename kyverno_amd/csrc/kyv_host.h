@@ -64,6 +64,12 @@ struct RuleMeta {
   bool has_validate = false;
   // keys (cache.MetaNamespaceKeyFunc) of the PolicyExceptions naming the rule, in candidate order (RuleDesc.exc)
   std::vector<std::string> exc_keys;
+  // `{{ request.object... }}` variables of the pattern / anyPattern (RuleDesc::dyn): per slot its key strings, and per
+  // variable leaf its slot, text (replaceBracesAndTrimSpaces) and JSON pointer inside the pattern document, for the
+  // "variable substitution failed" message (vars.go:395-399)
+  struct DynSite { uint32_t slot; std::string var, path; };
+  std::vector<std::vector<std::string>> dyn_segs;
+  std::vector<DynSite> dyn_sites;
 };
 
 // host-side text of a condition's references, for error messages (vars.go:395-399)

@@ -247,12 +247,14 @@ constexpr uint32_t COL_INDEX_MASK = (1u << COL_TYPE_SHIFT) - 1;
 constexpr uint64_t COL_ENTRIES_MAX = 0xFFFFFFF0ull;
 constexpr bool col_entries_fit32(uint64_t entries) { return entries <= COL_ENTRIES_MAX; }
 
-// L_DYN: a foreach pattern value that is exactly one element variable ({{element...}} / {{elementIndex}}); `exact`
-// holds its slot in the entry's dynamic-value list, resolved per element before the walk (vars.go:352-431 substitutes
-// a whole-string variable by its typed value)
+// L_DYN: a pattern value that is exactly one variable -- in a foreach pattern an element variable ({{element...}} /
+// {{elementIndex}}), in a plain pattern / anyPattern a `{{ request.object.<field chain> }}` variable; `exact` holds its
+// slot in the dynamic-value list of the foreach entry (ForeachEntry::dyn, resolved per element) or of the rule
+// (RuleDesc::dyn, resolved once per pair) before the walk (vars.go:352-431 substitutes a whole-string variable by its
+// typed value)
 enum LeafType : uint8_t { L_NIL = 0, L_BOOL = 1, L_FLOAT = 2, L_STR = 3, L_MAP = 4, L_ARR = 5, L_DYN = 6 };
 constexpr uint32_t FOREACH_MAX_NEST = 3;  // nested foreach levels below the top the device evaluates (deeper -> CPU)
-constexpr uint32_t MAX_DYN = 4;  // element variables per foreach pattern entry (more -> CPU fallback)
+constexpr uint32_t MAX_DYN = 4;  // distinct variables per foreach pattern entry / per pattern rule (more -> CPU fallback)
 struct Leaf {           // 32 bytes
   uint8_t type;
   uint8_t bval;
@@ -532,7 +534,11 @@ struct RuleDesc {
   uint32_t pre;          // precondition program (CondProg index) or NONE; RK_DENY: `root` is the deny program
   uint32_t exc;          // PolicyException candidates or NONE: pool offset of [n, then (mode, filters, nfilters) per
                          // candidate in FindExceptions order] (compiler.cpp compile_exceptions)
+  uint32_t dyn;          // RK_PATTERN / RK_ANYPATTERN: the rule's `{{ request.object.<path> }}` pattern variables (L_DYN
+                         // leaves, all alternatives together) or NONE: pool offset of [n, then per variable (nseg, path
+                         // column of the whole path, nseg key sids from the resource root)]
 };
+static_assert(sizeof(RuleDesc) == 64, "rule descriptor size");
 
 // ---------------------------------------------------------------- results
 enum Status : uint8_t { ST_NONE = 0, ST_PASS = 1, ST_FAIL = 2, ST_SKIP = 3, ST_ERROR = 4, ST_FALLBACK = 5, ST_PANIC = 6,
@@ -543,6 +549,9 @@ constexpr int NSTATUS = 8;
 constexpr uint8_t ST_MARK_PRE = 30u << 3;
 // on an error of a foreach rule: an element that is not a map under elementScope: true (validation.go:395-397)
 constexpr uint8_t ST_MARK_SCOPE = 29u << 3;
+// on an error of a pattern / anyPattern rule: a `{{ request.object... }}` variable of the pattern did not resolve
+// ("variable substitution failed", validation.go:294-297), decided before any pattern node ran
+constexpr uint8_t ST_MARK_VAR = 27u << 3;
 // transient (never returned): a PodSecurity pair pss_kernel left to pss_map_kernel (the map walk: exclusion
 // sub-pods, resources without path columns); low bits ST_NONE
 constexpr uint8_t ST_PSS_MAP = 28u << 3;

@@ -17,13 +17,28 @@ namespace kyv {
 // (kyv_wave.h).
 struct HostWalker {
   Stack stk;
+  Val dynv[MAX_DYN] = {};  // the rule's resolved pattern variables (resolve), used when the rule has any
+  bool has_dyn = false;
   KYV_HD void run(const View& v, uint32_t root, bool walk, const Node* R, const ResHeader* hp, uint32_t row,
                   const RuleDesc& rd, PatOut& out) {
     (void)row;
     out.status = ST_NONE;
-    if (walk) eval_pattern(v, root, NodeTab{R}, *hp, rd, stk, out);
+    if (walk) eval_pattern(v, root, NodeTab{R}, *hp, rd, stk, out, 0, has_dyn ? dynv : nullptr);
+  }
+  // substitutePatterns for one pair (validation.go:760-782): the values of the rule's variables (dyn == NONE: the
+  // rule has none); false: a key is missing on the way of some variable
+  KYV_HD bool resolve(const View& v, uint32_t dyn, bool walk, const Node* R, uint32_t row) {
+    (void)row;
+    has_dyn = dyn != NONE;
+    return !has_dyn || !walk || dyn_walk_values(v, NodeTab{R}, dyn, dynv);
   }
 };
+
+// Walkers whose `resolve` pair_walk calls before the alternatives (they hold the rule's `{{ request.object... }}`
+// variable values): the host walker and the interpreted wave walker. The runtime-compiled root functions resolve their
+// rule's variables themselves, with their root scope's column preload (jit.cpp).
+template <class W> struct walker_takes_dyn { static constexpr bool value = false; };
+template <> struct walker_takes_dyn<HostWalker> { static constexpr bool value = true; };
 
 // The alternative loop of validatePatterns over a callable that walks alternative `a` (alt(a, walk, po)): shared by
 // pair_walk (the alternative's root read from the rule) and the fused compiled walk kernels (jit.cpp), whose
@@ -45,7 +60,11 @@ KYV_HD uint8_t pair_walk_alts(bool pattern, uint32_t nalts, bool walk, uint32_t 
           rec = true;
           nfail++;
           break;
-        default: st = po.status; walk = false;  // fallback / panic / nondeterministic at this point of the walk
+        // fallback / panic / nondeterministic at this point of the walk, or ST_ERROR | ST_MARK_VAR from a compiled
+        // root function whose rule's variables did not resolve: the whole status byte, mark included, is compared
+        // above, so a marked error is not ST_ERROR (a failing alternative) but the pair's final status here, and no
+        // later alternative is walked
+        default: st = po.status; walk = false;
       }
     }
     FailRec fr;
@@ -74,9 +93,19 @@ KYV_HD uint8_t pair_walk(const View& v, const RuleDesc& rd, bool walk, uint32_t 
   const ResHeader* hp = v.hdr + r;
   const uint32_t nalts = rd.kind == RK_PATTERN ? 1 : rd.nalts;  // uniform across the wave
   const uint32_t row = r < v.nres ? r : NONE;
-  return pair_walk_alts(rd.kind == RK_PATTERN, nalts, walk, r, k, sink, [&](uint32_t a, bool w, PatOut& po) {
-    wk.run(v, rd.kind == RK_PATTERN ? rd.root : v.pool[rd.root + a], w, R, hp, row, rd, po);
-  });
+  // substitutePatterns (validation.go:294-297, :760-782) before the walk: the rule's variables, all alternatives
+  // together; a key missing on the way of any of them is the pair's error, whatever the walk would reach
+  if constexpr (walker_takes_dyn<Walker>::value) {
+    const bool sub_err = !wk.resolve(v, rd.dyn, walk, R, row);  // (rd.dyn is uniform across the wave)
+    const uint8_t st = pair_walk_alts(rd.kind == RK_PATTERN, nalts, walk && !sub_err, r, k, sink, [&](uint32_t a, bool w, PatOut& po) {
+      wk.run(v, rd.kind == RK_PATTERN ? rd.root : v.pool[rd.root + a], w, R, hp, row, rd, po);
+    });
+    return sub_err ? (uint8_t)(ST_ERROR | ST_MARK_VAR) : st;
+  } else {
+    return pair_walk_alts(rd.kind == RK_PATTERN, nalts, walk, r, k, sink, [&](uint32_t a, bool w, PatOut& po) {
+      wk.run(v, rd.kind == RK_PATTERN ? rd.root : v.pool[rd.root + a], w, R, hp, row, rd, po);
+    });
+  }
 }
 
 }  // namespace kyv

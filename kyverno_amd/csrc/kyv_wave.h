@@ -274,6 +274,70 @@ struct WaveWalker {
   int cap;
   bool rootmap;    // per lane (unused by the interpreter)
   uint32_t am = 0u;  // the chunk's all-maps facts (likewise)
+  // per lane: the rule's `{{ request.object... }}` pattern variables (RuleDesc::dyn) as path-column entries (type <<
+  // COL_TYPE_SHIFT | node, the node's `a`), loaded once at the start of the pair (resolve); a null value is type N_NULL
+  uint64_t dynv[MAX_DYN] = {0ull, 0ull, 0ull, 0ull};
+  bool has_dyn = false;  // wave-uniform
+
+  // substitutePatterns for the lanes with `walk` (validation.go:760-782): each variable's column entry at the resource
+  // row; a lane without an entry walks the keys from the root (the cold block), which tells a missing key (false: the
+  // pair's substitution error) from a null / non-map parent or a null value (null)
+  __device__ __forceinline__ bool resolve(const View& v, uint32_t dyn, bool walk, const Node* R, uint32_t row) {
+    has_dyn = dyn != NONE;
+    if (!has_dyn) return true;
+    static_assert(MAX_DYN == 4, "dynv / dyn_value hold four variables");
+    const uint32_t n0 = sld32(v.pool + dyn), n = n0 < MAX_DYN ? n0 : MAX_DYN;
+    uint32_t at = dyn + 1;
+    bool ok = true;
+#pragma unroll
+    for (uint32_t q = 0; q < MAX_DYN; q++) {
+      if (q >= n) break;
+      const uint32_t nseg = sld32(v.pool + at), col = sld32(v.pool + at + 1);
+      uint64_t e = (uint64_t)NONE;
+      if (walk && row != NONE && col != NONE && v.colv) {
+        KYV_ACCT_ADDK(2u, 0, 8);
+        e = *(const KYV_AS_GLOBAL uint64_t*)(v.colv + (uint32_t)(sld32(v.col_off + col) + row));
+      }
+      if (walk && (uint32_t)e == NONE) {  // cold: no entry (or no columns)
+        uint32_t cur = 0, t = N_MAP;
+        bool miss = false;
+        for (uint32_t s = 0; s < nseg && !miss; s++) {
+          const Node m = gnode(R + cur);
+          if (node_type(m) != N_MAP) { t = N_NULL; break; }
+          const uint32_t x = wmap_find(R, m.a, m.b, sld32(v.pool + at + 2 + s));
+          if (x == NONE) miss = true; else cur = x;
+        }
+        if (miss) ok = false;
+        else if (t == N_NULL) e = (uint64_t)((uint32_t)N_NULL << COL_TYPE_SHIFT);
+        else {
+          const Node m = gnode(R + cur);
+          e = ((uint64_t)m.a << 32) | (uint64_t)((node_type(m) << COL_TYPE_SHIFT) | (cur & COL_INDEX_MASK));
+        }
+      }
+      dynv[q] = e;
+      at += 2 + nseg;
+    }
+    return ok;
+  }
+  // the value of variable `slot` (wave-uniform), as the JSON context holds it
+  __device__ __forceinline__ Val dyn_value(const View& v, const Node* R, uint32_t slot) const {
+    uint64_t e = dynv[0];
+    if (slot == 1) e = dynv[1];
+    if (slot == 2) e = dynv[2];
+    if (slot == 3) e = dynv[3];
+    const uint32_t lo = (uint32_t)e, t = lo >> COL_TYPE_SHIFT, a = (uint32_t)(e >> 32);
+    Val x;
+    x.wsid = NONE; x.nsid = NONE; x.sid = NONE; x.i = 0; x.f = 0; x.t = t;
+    switch (t) {
+      case N_STR: x.sid = a; x.wsid = a; x.nsid = a; break;
+      case N_TRUE: x.wsid = SID_TRUE; break;
+      case N_FALSE: x.wsid = SID_FALSE; break;
+      case N_NULL: x.nsid = SID_ZERO; break;
+      case N_INT: case N_FLOAT: x = wvalue_node(v, gnode(R + (lo & COL_INDEX_MASK))); break;
+      default: break;  // a map / an array: leaf_match_dyn hands the pair to the CPU engine
+    }
+    return x;
+  }
 
   __device__ void run(const View& v, uint32_t root, bool walk, const Node* R, const ResHeader* hp, uint32_t row,
                       const RuleDesc& rd, PatOut& out) {
@@ -410,7 +474,14 @@ struct WaveWalker {
           const bool each = rt == N_ARR;
           const uint32_t cnt = go ? (each ? rnode.b : 1u) : 0u;
           bool fb = false, okv = true;
-          for (uint32_t i = 0; i < cnt && okv; i++) okv = wleaf_match(v, L, true, wvalue_of(v, R, each ? rnode.a + i : ern), &fb);
+          if (L.type == L_DYN) {  // (uniform) a variable leaf: pattern.Validate against the variable's value
+            if (!has_dyn) fb = go;
+            const Val pv = has_dyn && go ? dyn_value(v, R, L.exact) : wvalue_absent();
+            if (pv.t == N_MAP || pv.t == N_ARR) fb = true;  // another pattern, whatever the resource holds (eval_pattern)
+            for (uint32_t i = 0; i < cnt && okv && !fb; i++) okv = leaf_match_dyn(v, pv, wvalue_of(v, R, each ? rnode.a + i : ern), &fb);
+          } else {
+            for (uint32_t i = 0; i < cnt && okv; i++) okv = wleaf_match(v, L, true, wvalue_of(v, R, each ? rnode.a + i : ern), &fb);
+          }
           uint64_t d = wballot(go && fb);
           if (d & lbit) ost = ST_FALLBACK;
           dead |= d;
@@ -627,6 +698,7 @@ struct WaveWalker {
     out.status = ret.tmpl == NONE ? ST_ERROR : ST_FAIL;
   }
 };
+template <> struct walker_takes_dyn<WaveWalker> { static constexpr bool value = true; };
 
 // ---------------------------------------------------------------- runtime-compiled walkers (jit.cpp)
 // Per-lane state of one compiled pattern walk. The generated code is the per-lane recursion of eval_pattern
@@ -642,6 +714,8 @@ struct JW {
   uint32_t mbase;        // rule's first metadata-expansion site
   uint8_t ost;
   uint32_t am;           // the wave's all-maps facts (WaveFacts::maps; wave-uniform)
+  const Val* dyn = nullptr;  // the rule's resolved `{{ request.object... }}` pattern variables (its root function's
+                             // dv[]; L_DYN leaves index it with constants), nullptr for a rule without any
 };
 // one simple comparison with the atom's operator, flags and glob class as template constants (the generated
 // leaf code instantiates exactly the branches watom_simple would take for that atom)
@@ -711,6 +785,20 @@ __device__ __forceinline__ Val jvalue(const JW& w, uint32_t idx, uint32_t t, uin
     case N_FALSE: x.t = N_FALSE; x.wsid = SID_FALSE; return x;
     case N_NULL: x.t = N_NULL; x.nsid = SID_ZERO; return x;
     default: return wvalue_node(w.v, gnode(w.R + idx));
+  }
+}
+// value of a pattern variable whose column entry is present (index, type, a): the pattern side of leaf_match_dyn. A
+// number reads its row; a map / an array keeps its type only (leaf_match_dyn hands such a pair to the CPU engine)
+__device__ __forceinline__ Val jdyn_value(const View& v, const Node* R, uint32_t idx, uint32_t t, uint32_t a) {
+  Val x;
+  x.wsid = NONE; x.nsid = NONE; x.sid = NONE; x.i = 0; x.f = 0; x.t = t;
+  switch (t) {
+    case N_STR: x.sid = a; x.wsid = a; x.nsid = a; return x;
+    case N_TRUE: x.wsid = SID_TRUE; return x;
+    case N_FALSE: x.wsid = SID_FALSE; return x;
+    case N_NULL: x.nsid = SID_ZERO; return x;
+    case N_MAP: case N_ARR: return x;
+    default: return wvalue_node(v, gnode(R + idx));
   }
 }
 // MatchPattern's classification (validate.go:31-56), as at the end of eval_pattern
