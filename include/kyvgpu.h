@@ -202,6 +202,21 @@ typedef struct kyv_wave_facts_out {
   size_t bits_len;
 } kyv_wave_facts_out;
 int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out);
+/* The batch's column facts (diagnostics, read-only): a second per-wave plane beside the all-maps facts. Buffers as in
+ * kyv_batch_wave_facts.
+ *   rows  [waves]  one 64-bit word, "empty", per match wave of 64 resources (batch order, kyv_batch_wave_facts
+ *         `order`): bit j set = no resource of the wave has any value (of any type, null included) at list position j
+ *         of `bits`["lists"], in any parent the resource owns. With KYV_FACT_COLS=0 in the environment every word
+ *         reads 0, "nothing known", here and in the kernels.
+ *   bits  JSON {"lists": [path, ...]}: path segments as in kyv_batch_wave_facts; a list's path is that of the array
+ *         itself (without the final "[*]").
+ * bits_len receives the JSON's full length. */
+typedef struct kyv_col_facts_out {
+  uint64_t* rows; size_t rows_cap;
+  char* bits; size_t bits_cap;
+  size_t bits_len;
+} kyv_col_facts_out;
+int kyv_batch_col_facts(const kyv_batch* b, kyv_col_facts_out* out);
 /* What the batch's order within a kind is made of (diagnostics, read-only). The batch order is (kind class, shape
  * key, input index), ascending; the shape key of a resource packs, for each list position of the ruleset's patterns
  * and foreach loops, the largest length of an array the resource has there, so that the 64 resources of a match wave

@@ -67,6 +67,7 @@ EXPORTS = [
     "kyv_comm_gathered_status", "kyv_comm_gathered_failures", "kyv_comm_gather_report", "kyv_comm_reduce_counts", "kyv_results_batch_ms",
     "kyv_calibrate_fetch", "kyv_batch_wave_facts", "kyv_col_entries_fit32", "kyv_results_plan",
     "kyv_results_plan_slices", "kyv_batch_shape_keys", "kyv_batch_meta_keys",
+    "kyv_batch_col_facts",
 ]
 
 
@@ -74,6 +75,11 @@ class WaveFactsOut(ctypes.Structure):
     _fields_ = [("facts", ctypes.c_void_p), ("facts_cap", ctypes.c_size_t), ("hot", ctypes.c_void_p),
                 ("hot_cap", ctypes.c_size_t), ("order", ctypes.c_void_p), ("order_cap", ctypes.c_size_t),
                 ("bits", ctypes.c_void_p), ("bits_cap", ctypes.c_size_t), ("bits_len", ctypes.c_size_t)]
+
+
+class ColFactsOut(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("rows_cap", ctypes.c_size_t), ("bits", ctypes.c_void_p),
+                ("bits_cap", ctypes.c_size_t), ("bits_len", ctypes.c_size_t)]
 
 
 class ShapeKeysOut(ctypes.Structure):
@@ -172,6 +178,7 @@ def lib():
     L.kyv_batch_num_resources.restype = u32
     L.kyv_batch_stats_get.argtypes = [vp, ctypes.POINTER(BatchStats)]
     L.kyv_batch_wave_facts.argtypes = [vp, ctypes.POINTER(WaveFactsOut)]
+    L.kyv_batch_col_facts.argtypes = [vp, ctypes.POINTER(ColFactsOut)]
     L.kyv_batch_shape_keys.argtypes = [vp, ctypes.POINTER(ShapeKeysOut)]
     L.kyv_batch_meta_keys.argtypes = [vp, ctypes.c_int, ctypes.POINTER(MetaKeysOut)]
     L.kyv_eval.argtypes = [vp, vp, ctypes.POINTER(EvalOpts), ctypes.POINTER(vp)]

@@ -1251,6 +1251,10 @@ struct Resolver {
   // per-wave facts of the resource being resolved (kyv_layout.h WaveFacts): bit of a row space, -1 none
   const int8_t* space_bit;
   uint32_t notmaps = 0;
+  // column facts of the resource (kyv_layout.h ColFacts): empty bit of a trie node that holds a list, -1 none, and
+  // the positions where the resource has an entry
+  const int8_t* list_bit;
+  uint64_t present = 0;
   uint64_t entry(uint32_t x) const {
     return ((uint64_t)R[x].a << 32) | ((uint64_t)node_type(R[x]) << COL_TYPE_SHIFT) | x;
   }
@@ -1270,6 +1274,7 @@ struct Resolver {
       const auto& K = kids[t];
       auto hit = [&](uint32_t x, uint32_t kid) {
         if (colv) colv[(size_t)col_off[rs.trie[kid].col] + row] = entry(x);
+        if (list_bit[kid] >= 0) present |= 1ull << list_bit[kid];
         go(x, kid, row);
       };
       if (mn.b <= 2 * K.size() + 4) {  // merge join of two key-sorted lists
@@ -1401,9 +1406,12 @@ void resolve_path_columns(Batch& b, int threads) {
   b.col_off.assign(rs.ncols, 0);
   b.colv.clear();
   b.facts.assign((n + 63) / 64, WaveFacts{0u});  // .maps collects "some element is not an object" until the end
+  b.col_facts.assign((n + 63) / 64, ColFacts{0ull});  // likewise: "some entry", until the end
   if (rs.ncols == 0 || n == 0) return;
   std::vector<int8_t> space_bit(nsp, -1);
   for (size_t i = 0; i < rs.fact_spaces.size(); i++) space_bit[rs.fact_spaces[i]] = (int8_t)i;
+  std::vector<int8_t> list_bit(rs.trie.size(), -1);
+  for (size_t j = 0; j < rs.fact_lists.size() && j < COLFACT_BITS; j++) list_bit[rs.fact_lists[j]] = (int8_t)j;
   int T = std::max(1, threads);
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> kids(rs.trie.size());
   for (size_t t = 0; t < rs.trie.size(); t++) {
@@ -1425,9 +1433,11 @@ void resolve_path_columns(Batch& b, int threads) {
           if (!eligible(h)) continue;
           Resolver rv{rs, kids, b.nodes.data() + h.root, fill ? b.colv.data() : nullptr, b.col_off.data(), nexts[c].data(),
                       space_bit.data()};
+          rv.list_bit = list_bit.data();
           rv.go(0, 0, (uint32_t)r);
           // a wave's row is shared by the chunks (worker threads) whose resource ranges meet inside it: atomic OR
           if (fill && rv.notmaps) __atomic_fetch_or(&b.facts[r / 64].maps, rv.notmaps, __ATOMIC_RELAXED);
+          if (fill && rv.present) __atomic_fetch_or(&b.col_facts[r / 64].empty, rv.present, __ATOMIC_RELAXED);
         }
       }
     };
@@ -1475,11 +1485,18 @@ void resolve_path_columns(Batch& b, int threads) {
   for (auto& h : b.hdr) if (!eligible(h)) h.flags |= RF_MAGIC;
   const uint32_t defined = rs.fact_spaces.size() >= 32 ? 0xFFFFFFFFu : (1u << rs.fact_spaces.size()) - 1u;
   for (auto& f : b.facts) f.maps = ~f.maps & defined;
+  const uint64_t lists = rs.fact_lists.size() >= COLFACT_BITS ? ~0ull : (1ull << rs.fact_lists.size()) - 1ull;
+  for (auto& f : b.col_facts) f.empty = ~f.empty & lists;
 }
 
 uint32_t wave_maps_mask() {
   const char* e = getenv("KYV_FACT_MAPS");
   return e && atoi(e) == 0 ? 0u : 0xFFFFFFFFu;
+}
+
+uint64_t col_facts_mask() {
+  const char* e = getenv("KYV_FACT_COLS");
+  return e && atoi(e) == 0 ? 0ull : ~0ull;
 }
 
 std::string format_path(const Ruleset& rs, const Batch& b, uint32_t tmpl, const uint16_t* idx, const uint32_t* key) {

@@ -362,6 +362,53 @@ int kyv_batch_wave_facts(const kyv_batch* b, kyv_wave_facts_out* out) {
   }
 }
 
+// what the bits of a ColFacts row stand for, as JSON (kyvgpu.h kyv_batch_col_facts): the trie paths of
+// Ruleset::fact_lists
+static std::string col_fact_bits_json(const Ruleset& rs) {
+  std::vector<std::string> node_path(rs.trie.size());
+  std::function<void(uint32_t, const std::string&)> go = [&](uint32_t t, const std::string& path) {
+    const Ruleset::TrieNode& T = rs.trie[t];
+    node_path[t] = path;
+    const std::string sep = path.empty() ? "" : ",";
+    if (T.star != NONE) go(T.star, path + sep + "\"[*]\"");
+    for (const auto& kv : T.kids) {
+      std::string q = "\"";
+      for (unsigned char ch : rs.dict.strs[kv.first]) {
+        if (ch == '"' || ch == '\\') { q += '\\'; q += (char)ch; }
+        else if (ch < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", ch); q += b; }
+        else q += (char)ch;
+      }
+      go(kv.second, path + sep + q + "\"");
+    }
+  };
+  if (!rs.trie.empty()) go(0, "");
+  std::string js = "{\"lists\":[";
+  for (size_t i = 0; i < rs.fact_lists.size(); i++) js += (i ? ",[" : "[") + node_path[rs.fact_lists[i]] + "]";
+  return js + "]}";
+}
+
+int kyv_batch_col_facts(const kyv_batch* b, kyv_col_facts_out* out) {
+  if (!b || !out) return fail(KYV_EINVAL, "null argument");
+  try {
+    const Batch& x = *b->b;
+    const size_t nw = (x.hdr.size() + 63) / 64;
+    if (out->rows && out->rows_cap < nw) return fail(KYV_EINVAL, "buffer too small");
+    if (out->rows) {
+      const uint64_t m = col_facts_mask();
+      for (size_t w = 0; w < nw; w++) out->rows[w] = (w < x.col_facts.size() ? x.col_facts[w].empty : 0ull) & m;
+    }
+    const std::string js = col_fact_bits_json(*x.rs);
+    out->bits_len = js.size();
+    if (out->bits) {
+      if (out->bits_cap < js.size() + 1) return fail(KYV_EINVAL, "buffer too small");
+      memcpy(out->bits, js.c_str(), js.size() + 1);
+    }
+    return KYV_OK;
+  } catch (std::exception& e) {
+    return fail(KYV_EINTERNAL, e.what());
+  }
+}
+
 // the "[*]" paths a shape key is made of, most significant field first, as JSON (kyvgpu.h kyv_batch_shape_keys)
 static std::string shape_key_paths_json(const Ruleset& rs, bool ordered) {
   const std::vector<uint32_t> nodes = shape_key_nodes(rs);

@@ -2798,6 +2798,7 @@ void build_path_trie(Ruleset& rs) {
   // entries of pnodes that conflicted after their first visit assigned columns: clear the whole subtree
   // (a conflicting subtree is walked with t == NONE, which already cleared its entries' columns)
   assign_wave_facts(rs);
+  assign_col_facts(rs);
   assign_meta_classes(rs);
 }
 
@@ -2824,6 +2825,17 @@ void assign_wave_facts(Ruleset& rs) {
     if (map_child) spaces.insert(rs.col_rowspace[rs.pn_self[pn]]);
   }
   for (uint32_t s2 : spaces) if (rs.fact_spaces.size() < FACT_BITS) rs.fact_spaces.push_back(s2);
+}
+
+// Column facts (round 14, Batch::col_facts, kyv_layout.h ColFacts): the numbering of the empty bits.
+//   fact_lists: the trie nodes that hold an array ("[*]" child) and have an entry column, in trie (node index) order,
+//               at most COLFACT_BITS; empty bit j of a wave = none of the wave's resources has an entry in the entry
+//               column of fact_lists[j], so neither that column nor the position's length column holds anything for
+//               the wave
+void assign_col_facts(Ruleset& rs) {
+  rs.fact_lists.clear();
+  for (uint32_t t = 0; t < rs.trie.size() && rs.fact_lists.size() < COLFACT_BITS; t++)
+    if (rs.trie[t].star != NONE && rs.trie[t].col != NONE) rs.fact_lists.push_back(t);
 }
 
 // Meta-key classes (round 10, kyv_layout.h MetaClass): the distinct wildcard metadata sites of pattern rules at a

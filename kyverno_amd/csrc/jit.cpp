@@ -45,6 +45,15 @@ int jit_jc_chains_mode() {
   return e ? (atoi(e) != 0) : jit_meta_keys_on() ? 1 : 0;
 }
 
+int jit_col_facts_mode() {
+  for (const char* n : {"KYV_JC_PRELOAD", "KYV_META_KEYS"}) {
+    const char* e = getenv(n);
+    if (e && atoi(e) == 0) return 0;
+  }
+  const char* e = getenv("KYV_JIT_COLFACTS");
+  return e ? (atoi(e) & 1) : 1;
+}
+
 namespace {
 
 struct Gen {
@@ -93,11 +102,32 @@ struct Gen {
   std::vector<int8_t> meta_pos;                  // pnode -> static position whose metadata flags the flattener
                                                  // computed: 0 root, 1 spec.template, 2 spec.jobTemplate.spec.template
 
-  explicit Gen(const Ruleset& r, int meta_keys_mode = -1)
+  // Column facts (kyv_layout.h ColFacts, KYV_JIT_COLFACTS bit 0): a preload of the entry column or the length column of
+  // a "[*]" position that has an empty bit takes row NONE where the wave's bit is set -- the load's own "no row" case,
+  // as the all-maps fact's `em ? NONE : er` below: no scalar branch around it, and the value reads as absent, which is
+  // what it is. empty_bit: column -> bit. The wave's word is `ce` in a root function and w.ce below it.
+  const int colfacts;
+  std::map<uint32_t, uint32_t> empty_bit;
+  // row expression `rowx` of a load of column `col`, where the wave's empty word is `ce`
+  std::string fact_row(uint32_t col, const std::string& rowx, const std::string& ce) const {
+    auto it = empty_bit.find(col);
+    if (it == empty_bit.end()) return rowx;
+    return "((" + ce + " >> " + std::to_string(it->second) + "u) & 1ull) ? NONE : " + rowx;
+  }
+
+  explicit Gen(const Ruleset& r, int meta_keys_mode = -1, int colfacts_mode = -1)
       : rs(r), meta_keys(meta_keys_mode < 0 ? jit_meta_keys_on() : meta_keys_mode != 0), emitted(r.pnodes.size(), 0), slot_meta(r.pnodes.size(), -1), wild_src(r.pentries.size()),
         slot(r.pentries.size(), -1), slot_alen(r.pnodes.size(), -1),
         slot_elen(r.pentries.size(), -1), scope_of(r.pnodes.size()), scoped(r.pnodes.size(), 0),
-        node_mbase(r.pnodes.size(), NONE), meta_pos(r.pnodes.size(), -1) {}
+        node_mbase(r.pnodes.size(), NONE), meta_pos(r.pnodes.size(), -1),
+        colfacts(colfacts_mode < 0 ? jit_col_facts_mode() : colfacts_mode) {
+    if (colfacts & 1)
+      for (size_t j = 0; j < rs.fact_lists.size() && j < COLFACT_BITS; j++) {
+        const Ruleset::TrieNode& T = rs.trie[rs.fact_lists[j]];
+        empty_bit[T.col] = (uint32_t)j;
+        if (T.lencol != NONE) empty_bit[T.lencol] = (uint32_t)j;
+      }
+  }
 
   // static key path of the pattern maps below a rule root (plain key entries only), for meta_pos
   void mark_paths(uint32_t pn, uint32_t mbase, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, int depth) {
@@ -200,14 +230,16 @@ struct Gen {
   const std::vector<uint32_t>& scope_cols(uint32_t root) { scope(root); return scope_of[root]; }
   // preload of scope `root`'s columns at row expression `rowx` into array `name`
   // (`rd`: the column read, jself(w, ...) inside the walk, jc_col(v, ...) before the walker state exists)
-  std::string preload(uint32_t root, const std::string& name, const std::string& rowx, const char* rd = "jself(w, ") {
+  // (`ce`: the name of the wave's empty-list word there, `ce` in a root function, w.ce below it)
+  std::string preload(uint32_t root, const std::string& name, const std::string& rowx, const char* rd = "jself(w, ",
+                      const char* ce = "w.ce") {
     scope(root);
     const auto& L = scope_of[root];
     std::ostringstream o;
     o << "uint64_t " << name << "[" << std::max<size_t>(1, L.size()) << "];";
     for (size_t i = 0; i < L.size(); i++) {
       if (L[i] & MK_COL) { o << meta_load(L, i, name, rowx); continue; }
-      o << " " << name << "[" << i << "] = " << rd << u(L[i]) << ", " << rowx << ");";
+      o << " " << name << "[" << i << "] = " << rd << u(L[i]) << ", " << fact_row(L[i], rowx, ce) << ");";
     }
     return o.str();
   }
@@ -712,7 +744,25 @@ struct CondGen {
   uint32_t cur_etpos = NONE;  // element trie position of the program being generated (stream_cond)
   std::unordered_map<uint64_t, std::string> progs;  // (program, element trie position) -> function name
 
-  CondGen(const Ruleset& r, int mode) : rs(r), chains(mode < 0 ? jit_jc_chains_mode() != 0 : mode != 0) {}
+  CondGen(const Ruleset& r, int mode, int colfacts_mode)
+      : rs(r), colfacts(colfacts_mode), chains(mode < 0 ? jit_jc_chains_mode() != 0 : mode != 0) {
+    if (colfacts & 1)
+      for (size_t j = 0; j < rs.fact_lists.size() && j < COLFACT_BITS; j++) empty_bit[rs.fact_lists[j]] = (uint32_t)j;
+  }
+  // Column facts (kyv_layout.h ColFacts::empty, KYV_JIT_COLFACTS bit 0): the entry read of a list position (force) and
+  // its length column read (open_elems) take row NONE where the wave's empty bit of that position is set: the members
+  // of spec.[ephemeralContainers, initContainers, containers][] that no resource of the wave has cost no load. The
+  // wave's word is read once per rule function (jr<k>: `ce = jc_empty(v, r)`, one scalar load) and handed down to the
+  // operand and program functions as a parameter behind `r` (rsig / rarg; nothing without the facts)
+  const int colfacts;
+  std::string rsig() const { return (colfacts & 1) ? "uint32_t r, const uint64_t ce, " : "uint32_t r, "; }
+  std::string rarg() const { return (colfacts & 1) ? "(v, R, r, ce, " : "(v, R, r, "; }
+  std::map<uint32_t, uint32_t> empty_bit;  // trie position that holds a list -> its bit
+  std::string fact_row(uint32_t tpos, const std::string& row) const {
+    auto it = empty_bit.find(tpos);
+    if (it == empty_bit.end()) return row;
+    return "(((ce >> " + std::to_string(it->second) + "u) & 1ull) ? NONE : " + row + ")";
+  }
   static std::string u(uint32_t x) { return std::to_string(x) + "u"; }
   std::string fresh(const char* p) { return std::string(p) + std::to_string(uid++); }
 
@@ -746,7 +796,7 @@ struct CondGen {
     if (x.lz.empty()) return x;
     V y{fresh("vi"), fresh("vt"), fresh("va"), x.row, x.tpos, false, {}};
     out << "  uint32_t " << y.i << ", " << y.t << ", " << y.a << ";\n"
-        << "  if (" << x.row << " != NONE) jc_field_e(jc_col(v, " << u(tcol(x.tpos)) << ", " << x.row << "), &" << y.i << ", &"
+        << "  if (" << x.row << " != NONE) jc_field_e(jc_col(v, " << u(tcol(x.tpos)) << ", " << fact_row(x.tpos, x.row) << "), &" << y.i << ", &"
         << y.t << ", &" << y.a << ");\n"
         << "  else {\n    " << y.i << " = " << x.i << ";\n";
     for (uint32_t key : x.lz)
@@ -786,7 +836,7 @@ struct CondGen {
     const std::string cnt = fresh("cn"), aa = fresh("aa"), eb = fresh("eb"), j = fresh("j");
     const uint32_t st = tstar(x.tpos);
     out << "  { uint32_t " << cnt << " = 0u, " << aa << " = 0u, " << eb << " = NONE;\n"
-        << "  if (" << (x.key ? "false" : "jc_arr(v, R, " + x.i + ", " + x.t + ", " + x.a + ", " + x.row + ", " +
+        << "  if (" << (x.key ? "false" : "jc_arr(v, R, " + x.i + ", " + x.t + ", " + x.a + ", " + (tlen(x.tpos) == NONE ? x.row : fact_row(x.tpos, x.row)) + ", " +
                                               (tlen(x.tpos) == NONE ? std::string("NONE") : u(tlen(x.tpos))) + ", &" + cnt +
                                               ", &" + aa + ", &" + eb + ")")
         << ") {\n" << on_arr << (unroll ? "  KYV_JC_UNROLL\n" : "")
@@ -932,7 +982,7 @@ struct CondGen {
     std::ostringstream save;
     save.swap(out);
     out << "static __device__ __forceinline__ int " << name
-        << "(const View& v, const Node* R, uint32_t r, uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, uint32_t* L, "
+        << "(const View& v, const Node* R, " << rsig() << "uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, uint32_t* L, "
            "bool* lst, uint32_t* cur, uint32_t* ln, uint32_t* lit) {\n"
            "  *lst = false; *cur = NONE; *ln = 0u; *lit = NONE;\n";
     uint32_t i = 1, orlit = NONE;
@@ -1002,7 +1052,7 @@ struct CondGen {
     std::ostringstream save;
     save.swap(out);
     out << "static __device__ __forceinline__ int " << name
-        << "(const View& v, const Node* R, uint32_t r, uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, "
+        << "(const View& v, const Node* R, " << rsig() << "uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, "
            "bool* lst, uint32_t* cur, uint32_t* ln, uint32_t* lit, uint32_t* sm, uint32_t* sf) {\n"
            "  *lst = false; *cur = NONE; *ln = 0u; *lit = NONE; (void)sm; (void)sf;\n";
     V x = root == JR_OBJECT ? decl("0u", "T_UNK", "0u", "r", 0u, false) : decl("ei", "et", "ea", "erow", etpos, false);
@@ -1063,7 +1113,7 @@ struct CondGen {
     const std::string l = fresh("jl"), cc = fresh("jc"), n = fresh("jn"), t = fresh("jt"), s = fresh("js"), m = fresh("sm"),
                       fb = fresh("sf");
     out << "  bool " << l << "; uint32_t " << cc << ", " << n << ", " << t << ", " << m << " = 0u, " << fb << " = 0u;\n"
-        << "  const int " << s << " = " << f << "(v, R, r, ei, et, ea, erow, &" << l << ", &" << cc << ", &" << n << ", &" << t
+        << "  const int " << s << " = " << f << rarg() << "ei, et, ea, erow, &" << l << ", &" << cc << ", &" << n << ", &" << t
         << ", &" << m << ", &" << fb << ");\n"
         << "  if (" << s << " == JS_FB) return CR_FB;\n  if (" << s << " == JS_NOTFOUND) return CP_ERROR;\n"
         << "  if (" << l << ") {\n";
@@ -1141,7 +1191,7 @@ struct CondGen {
         const std::string f = operand_fn(o, etpos);
         const std::string l = fresh("jl"), c = fresh("jc"), n = fresh("jn"), t = fresh("jt"), s = fresh("js");
         out << "  bool " << l << "; uint32_t " << c << ", " << n << ", " << t << ";\n"
-            << "  const int " << s << " = " << f << "(v, R, r, ei, et, ea, erow, " << slot << ", &" << l << ", &" << c
+            << "  const int " << s << " = " << f << rarg() << "ei, et, ea, erow, " << slot << ", &" << l << ", &" << c
             << ", &" << n << ", &" << t << ");\n";
         if (check) out << "  if (" << s << " == JS_FB) return CR_FB;\n  if (" << s << " == JS_NOTFOUND) return CP_ERROR;\n";
         else out << "  (void)" << s << ";\n";
@@ -1240,7 +1290,7 @@ struct CondGen {
     const std::string b = out.str();
     out.swap(save);
     defs << "static __device__ __forceinline__ int " << name
-         << "(const View& v, const Node* R, uint32_t r, uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, uint32_t* L) {\n"
+         << "(const View& v, const Node* R, " << rsig() << "uint32_t ei, uint32_t et, uint32_t ea, uint32_t erow, uint32_t* L) {\n"
          << "  (void)ei; (void)et; (void)ea; (void)erow;\n"
          << b << "}\n";
     progs[key] = name;
@@ -1255,7 +1305,7 @@ struct CondGen {
     out << "  do {\n";
     if (FE->scope == 2) out << "  if (jc_type(R, " << e.i << ", " << e.t << ") != N_MAP) return ST_ERROR | ST_MARK_SCOPE;\n";
     out << "  bool err = false;\n";
-    const std::string args = "(v, R, r, " + e.i + ", " + e.t + ", " + e.a + ", " + e.row + ", L)";
+    const std::string args = rarg() + e.i + ", " + e.t + ", " + e.a + ", " + e.row + ", L)";
     if (FE->pre != NONE) {
       const std::string f = prog_fn(FE->pre, e.tpos);
       out << "  { const int c = " << f << args << ";\n"
@@ -1421,7 +1471,7 @@ struct CondGen {
     out << "  if (hnn >= (1u << COL_TYPE_SHIFT)) return ST_FALLBACK;  // no path columns for this resource\n"
         << "  const Node* R = v.nodes + hroot;\n"
         << "  const uint32_t ei = NONE, et = T_UNK, ea = 0u, erow = NONE;\n";
-    const std::string args = "(v, R, r, ei, et, ea, erow, L)";
+    const std::string args = rarg() + "ei, et, ea, erow, L)";
     if (rd.pre != NONE) {
       const std::string f = prog_fn(rd.pre, NONE);
       out << "  { const int c = " << f << args << ";\n"
@@ -1455,7 +1505,8 @@ struct CondGen {
     const std::string b = out.str();
     out.swap(save);
     // inlined into its rule's kernel (kyv_jit_cond_<k>): no call frame (callee-saved registers in scratch memory)
-    defs << "static __device__ __forceinline__ uint8_t jr" << k << "(const View& v, uint32_t r, uint32_t hroot, uint32_t hnn, uint32_t* L) {\n" << b << "}\n";
+    defs << "static __device__ __forceinline__ uint8_t jr" << k << "(const View& v, uint32_t r, uint32_t hroot, uint32_t hnn, uint32_t* L) {\n"
+         << ((colfacts & 1) ? "  const uint64_t ce = jc_empty(v, r);  // the wave's empty-list facts\n  (void)ce;\n" : "") << b << "}\n";
   }
 };
 
@@ -1531,8 +1582,12 @@ static std::string meta_signature(const Ruleset& rs, const RuleDesc& rd) {
 }
 
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond,
-                       std::vector<uint16_t>* jit_shape, int meta_keys, int jc_chains) {
-  Gen g(rs, meta_keys);
+                       std::vector<uint16_t>* jit_shape, int meta_keys, int jc_chains, int col_facts) {
+  Gen g(rs, meta_keys, col_facts);
+  // with the column facts the root functions, the walkers and the shape table take the wave's empty word (`ce`)
+  // beside `am`; without them the source is that of the rounds before, byte for byte
+  const bool cf = (g.colfacts & 1) != 0;
+  const std::string ce_par = cf ? ", const uint64_t ce" : "", ce_arg = cf ? ", ce" : "", ce_set = cf ? "  w.ce = ce;\n" : "";
   jit_rules->assign(rs.rules.size(), 0);
   if (jit_shape) jit_shape->assign(rs.rules.size(), 0);
   if (jit_cond) jit_cond->assign(rs.rules.size(), 0);
@@ -1542,7 +1597,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   const size_t cap = getenv("KYV_JIT_MAX_RULES") ? (size_t)atol(getenv("KYV_JIT_MAX_RULES")) : 1024;
   // compiled condition rules: deny / foreach rules with JMESPath operands (the rest of the interpreted
   // match_kernel<true>'s rules); KYV_JIT_COND=0 leaves them all on the interpreter
-  CondGen cg(rs, jc_chains);
+  CondGen cg(rs, jc_chains, g.colfacts);
   std::vector<uint32_t> crules;
   const bool cond_on = !getenv("KYV_JIT_COND") || atoi(getenv("KYV_JIT_COND")) != 0;
   for (size_t k = 0; k < rs.rules.size() && cond_on && crules.size() < cap; k++) {
@@ -1814,13 +1869,13 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
       if (rep_of[r] == r)  // one root function per pattern shape
       src << "static __device__ __forceinline__ void root" << r
           << "(const View& v, const Node* R, const ResHeader* hp, uint32_t row, uint32_t mbase, bool rootmap, bool walk,\n"
-             "    PatOut& out, const uint32_t am) {\n"
-             "  " << g.preload(r, "pc", "row", "jc_col(v, ") << "\n"
+             "    PatOut& out, const uint32_t am" << ce_par << ") {\n"
+             "  " << g.preload(r, "pc", "row", "jc_col(v, ", "ce") << "\n"
           << g.dyn_preload(dyn_of(r)) <<
              "  if (!walk) return;\n"
              "#ifdef KYV_EXP_JIT_PRELOAD\n  { uint64_t x = 0; for (auto q : pc) x ^= q; out.status = x == 0x123456789ull ? ST_FAIL : ST_PASS; return; }\n#endif\n"
           << g.dyn_decode(dyn_of(r)) <<
-             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n"
+             "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n" << ce_set <<
              "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
              "  jfinish(w, r, out);\n"
              "}\n";
@@ -1885,7 +1940,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         const auto& L = g.scope_of[r];
         src << "static __device__ __forceinline__ void rootc" << r << "_" << gi
             << "(const View& v, const Node* R, const ResHeader* hp, uint32_t row, uint32_t mbase, bool rootmap, bool walk,\n"
-               "    PatOut& out, const uint64_t* jcc, const uint32_t am) {\n"
+               "    PatOut& out, const uint64_t* jcc, const uint32_t am" << ce_par << ") {\n"
                "  const uint32_t lane = threadIdx.x & 63u;\n"
                "  (void)lane;\n"
                "  uint64_t pc[" << std::max<size_t>(1, L.size()) << "];";
@@ -1893,13 +1948,13 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
           auto it = cslot.find(L[i]);
           if (it != cslot.end()) src << " pc[" << i << "] = jcc[" << it->second * 64u << "u + lane];";
           else if (L[i] & Gen::MK_COL) src << Gen::meta_load(L, i, "pc", "row");
-          else src << " pc[" << i << "] = jc_col(v, " << Gen::u(L[i]) << ", row);";
+          else src << " pc[" << i << "] = jc_col(v, " << Gen::u(L[i]) << ", " << g.fact_row(L[i], "row", "ce") << ");";
         }
         src << "\n"
             << g.dyn_preload(dyn_of(r)) <<
                "  if (!walk) return;\n"
             << g.dyn_decode(dyn_of(r)) <<
-               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n"
+               "  JW w{v, R, hp, 0ull, 0ull, Keys{NONE, NONE}, 0ull, mbase, (uint8_t)ST_NONE, am" << (dyn_of(r) != NONE ? ", dv" : "") << "};\n" << ce_set <<
                "  Ret r = p" << r << "(w, 0u, rootmap ? (uint32_t)N_MAP : T_UNK, 0u, row, pc);\n"
                "  jfinish(w, r, out);\n"
                "}\n";
@@ -1918,6 +1973,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     src << "struct JitWalker" << gi << " {\n"
            "  bool rootmap;\n"
            "  uint32_t am;\n"
+        << (cf ? "  uint64_t ce;  // the wave's empty-list facts (walk_chunks sets it)\n  static constexpr bool kColFacts = true;\n" : "") <<
            "  __device__ __forceinline__ void run(const View& v, uint32_t root, bool walk, const Node* R, const ResHeader* hp,\n"
            "                                     uint32_t row, const RuleDesc& rd, PatOut& out) {\n"
            "    out.status = ST_NONE; out.idx = 0; out.tmpl = NONE; out.key0 = NONE; out.key1 = NONE;\n"
@@ -1933,12 +1989,12 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     if (roots.size() <= 256) {
       for (auto& br : by_rep) {
         for (uint32_t r : br.second) src << "      case " << r << "u:";
-        src << " root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am); break;\n";
+        src << " root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am" << ce_arg << "); break;\n";
       }
     } else {
       uint32_t si = 0;
       for (auto& br : by_rep) {
-        src << "      case " << si++ << "u: root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am); break;\n";
+        src << "      case " << si++ << "u: root" << br.first << "(v, R, hp, row, rd.meta_sites, rootmap, walk, out, am" << ce_arg << "); break;\n";
       }
     }
     src << "      default: if (walk) out.status = ST_FALLBACK;\n"
@@ -1977,6 +2033,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
              "    const uint32_t row = r < v.nres ? r : NONE;\n"
              "    const bool rootmap = (hflags & RF_ROOT_MAP) != 0;\n"
              "    const uint32_t am = wave_maps(v, w);\n"
+          << (cf ? "    const uint64_t ce = wave_cols(v, w).empty;\n    (void)ce;\n" : "") <<
              "    (void)lane; (void)hp; (void)rootmap; (void)hnn; (void)am;\n";
       if (!conds.empty()) src << "    __shared__ uint32_t jl[" << jc_lds << "];\n";
       if (ncslots) {
@@ -2001,7 +2058,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
           src << "    if (";
           size_t j = 0;
           for (const auto& e : wm) src << (j++ ? " | " : "") << "(jsl[" << e.first << "] & " << e.second << "u)";
-          src << ") jcc[" << cslot[cu.first] * 64u << "u + lane] = jc_col(v, " << Gen::u(cu.first) << ", row);\n";
+          src << ") jcc[" << cslot[cu.first] * 64u << "u + lane] = jc_col(v, " << Gen::u(cu.first) << ", " << g.fact_row(cu.first, "row", "ce") << ");\n";
         }
       }
       for (size_t j = 0; j < part.size(); j++) {
@@ -2026,10 +2083,10 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
         const uint32_t root = rule_roots[i].second[a];
         if (ncslots)
           src << "            case " << a << "u: rootc" << rep_of[root] << "_" << gi << "(vl, R, hp, row, " << Gen::u(rd.meta_sites)
-              << ", rootmap, wk, po, jcc, am); break;\n";
+              << ", rootmap, wk, po, jcc, am" << ce_arg << "); break;\n";
         else
           src << "            case " << a << "u: root" << rep_of[root] << "(vl, R, hp, row, " << Gen::u(rd.meta_sites)
-              << ", rootmap, wk, po, am); break;\n";
+              << ", rootmap, wk, po, am" << ce_arg << "); break;\n";
       }
       src << "            default: break;\n"
              "          }\n"
@@ -2106,8 +2163,9 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
   if (!shape_list.empty()) {
     // every root function a shape needs is already in the source (its users are covered rules of some group)
     src << "struct JitShapes {\n"
+        << (cf ? "  static constexpr bool kColFacts = true;  // run() takes the wave's empty-list facts (walk_shapes)\n" : "") <<
            "  __device__ __forceinline__ void run(const View& v, const ShapeOut& so, uint32_t r, bool active, uint32_t hflags,\n"
-           "                                     uint32_t hroot, uint32_t cls, const uint32_t am) {\n"
+           "                                     uint32_t hroot, uint32_t cls, const uint32_t am" << ce_par << ") {\n"
            "    const Node* R = v.nodes + hroot;\n"
            "    const ResHeader* hp = v.hdr + r;\n"
            "    const uint32_t row = r < v.nres ? r : NONE;\n"
@@ -2122,7 +2180,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
              "        ShapeSink sink{so.rec + (size_t)" << S << " * v.nres + r};\n"
              "        uint8_t st = pair_walk_alts(true, 1u, gated && !magic, r, 0u, sink, [&](uint32_t, bool wk, PatOut& po) {\n"
              "          po.status = ST_NONE; po.idx = 0; po.tmpl = NONE; po.key0 = NONE; po.key1 = NONE;\n"
-             "          root" << shape_list[si].first << "(v, R, hp, row, " << Gen::u(shape_list[si].second) << ", rootmap, wk, po, am);\n"
+             "          root" << shape_list[si].first << "(v, R, hp, row, " << Gen::u(shape_list[si].second) << ", rootmap, wk, po, am" << ce_arg << ");\n"
              "        });\n"
              "        if (magic) st = ST_FALLBACK;\n"
              "        if (gated) { so.st[(size_t)" << S << " * v.nres + r] = st; KYV_ACCT_ADD(1, 1); }\n"
@@ -2202,7 +2260,7 @@ std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::
     src << "extern \"C\" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu("
         << (gwpe[gi] == -2 ? "KYV_JIT_WPE_LIGHT" : "KYV_JIT_WPE") << ")))\n"
            "kyv_jit_walk_" << gi << "(const kyv::View* __restrict__ vp, kyv::DevOut o, kyv::WorkLists wl, kyv::ChunkMap cm) {\n"
-           "  kyv::JitWalker" << gi << " wk{false, 0u};\n"
+           "  kyv::JitWalker" << gi << " wk{false, 0u" << (cf ? ", 0ull" : "") << "};\n"
            "  kyv::walk_chunks(*vp, o, wl, cm, wk);\n"
            "}\n";
   // fused kernels: one workgroup (one wave) per match wave of the batch. A fused kernel holds every direct rule of its

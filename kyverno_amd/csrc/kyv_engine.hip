@@ -423,6 +423,7 @@ struct DeviceResults {
   const MetaKeyRow* view_meta = nullptr;
   const HotHdr* view_hot = nullptr;
   uint32_t view_fact_and = 0;
+  uint64_t view_col_and = 0;
   // pattern-shape tables (kyv_jit_shapes, round 5): [shape][res] verdict bytes and records, the per-class shape gate
   uint8_t* shape_st = nullptr;
   FailRec* shape_rec = nullptr;
@@ -463,7 +464,7 @@ struct DevBatch {
   DeviceResults* out = nullptr;  // result buffers + stream, resident across evaluations
   uint8_t* base = nullptr;
   size_t bytes = 0;
-  size_t o_nodes, o_hdr, o_hot, o_facts, o_faux, o_soff, o_slen, o_sflags, o_sdur, o_sqty, o_sf64, o_heap, o_nsloff, o_nslkv, o_gate,
+  size_t o_nodes, o_hdr, o_hot, o_facts, o_cfacts, o_faux, o_soff, o_slen, o_sflags, o_sdur, o_sqty, o_sf64, o_heap, o_nsloff, o_nslkv, o_gate,
       o_colv, o_coloff, o_pe, o_supper = SIZE_MAX, o_srx = SIZE_MAX;
   uint32_t* gmask = nullptr;   // [string][words] glob-mask bits, computed on the device once per batch
   uint32_t gmask_words = 0;
@@ -521,6 +522,7 @@ static DevBatch* upload_batch(const Batch& b, int device) {
   d->o_hdr = p.add(b.hdr);
   d->o_hot = p.add(b.hot);
   d->o_facts = p.add(b.facts);
+  d->o_cfacts = p.add(b.col_facts);
   d->o_faux = p.add(b.faux);
   d->o_soff = p.add(b.str_off);
   d->o_slen = p.add(b.str_len);
@@ -563,6 +565,7 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
     v.hdr = (const ResHeader*)(bbase + db->o_hdr);
     v.hot = hot_plane_on() && b.hot.size() == b.hdr.size() ? (const HotHdr*)(bbase + db->o_hot) : nullptr;
     v.facts = b.facts.size() == (b.hdr.size() + 63) / 64 ? (const WaveFacts*)(bbase + db->o_facts) : nullptr;
+    v.col_facts = b.col_facts.size() == (b.hdr.size() + 63) / 64 ? (const ColFacts*)(bbase + db->o_cfacts) : nullptr;
     v.faux = (const FloatAux*)(bbase + db->o_faux);
     v.str_off = (const uint32_t*)(bbase + db->o_soff);
     v.str_len = (const uint32_t*)(bbase + db->o_slen);
@@ -587,6 +590,7 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
     v.nodes = b.nodes.data(); v.hdr = b.hdr.data(); v.faux = b.faux.data();
     v.hot = hot_plane_on() && b.hot.size() == b.hdr.size() ? b.hot.data() : nullptr;
     v.facts = b.facts.size() == (b.hdr.size() + 63) / 64 ? b.facts.data() : nullptr;
+    v.col_facts = b.col_facts.size() == (b.hdr.size() + 63) / 64 ? b.col_facts.data() : nullptr;
     v.str_off = b.str_off.data(); v.str_len = b.str_len.data(); v.str_flags = b.str_flags.data();
     v.str_dur = b.str_dur.data(); v.str_qty = b.str_qty.data(); v.str_f64 = b.str_f64.data();
     v.heap = b.heap.data(); v.nsl_off = b.nsl_off.data(); v.nsl_kv = b.nsl_kv.data();
@@ -599,6 +603,7 @@ static View make_view(const Ruleset& rs, const Batch& b, const uint8_t* rbase, c
   v.gate_words = b.gate_words;
   v.nres = (uint32_t)b.hdr.size();
   v.fact_and = wave_maps_mask();
+  v.col_and = col_facts_mask();
   v.nrules = (uint32_t)rs.rules.size();
   if (dr) {
     v.rules = (const RuleDesc*)(rbase + dr->o_rules);
@@ -1149,7 +1154,9 @@ static bool ensure_jit(Ruleset& rs, DevRuleset* dr) {
     try {
       rs.jit_meta_keys = jit_meta_keys_on() && !rs.meta_classes.empty();
       rs.jit_jc_chains = jit_jc_chains_mode();
-      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains);
+      rs.jit_col_facts = jit_col_facts_mode();
+      std::string src = jit_source(rs, &rs.jit_rules, &rs.jit_cond, &rs.jit_shape, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains,
+                                   rs.jit_col_facts);
       rs.jit_nshapes = 0;
       for (auto x : rs.jit_shape) rs.jit_nshapes = std::max<uint32_t>(rs.jit_nshapes, x);
       bool any = false;
@@ -1223,7 +1230,8 @@ static bool ensure_jit_acct(Ruleset& rs, DevRuleset* dr) {
     std::vector<uint8_t> jr, jc;
     // (the switches as the product source had them: the accounting kernels read the plane exactly when it is filled,
     // and count the condition kernels' loads as the product kernels issue them)
-    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc, nullptr, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains), nullptr, true);
+    rs.jit_code_acct = jit_compile(jit_source(rs, &jr, &jc, nullptr, rs.jit_meta_keys ? 1 : 0, rs.jit_jc_chains, rs.jit_col_facts),
+                                   nullptr, true);
   }
   HIP_OK(hipModuleLoadData(&dr->amod, rs.jit_code_acct.data()));
   dr->afns.resize(dr->jfns.size());
@@ -2063,7 +2071,7 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     stream_get(&d.stream, &d.e0, &d.e1);
     HIP_OK(dmalloc(&d.view, sizeof(View)));
     HIP_OK(hipMemcpy(d.view, &v, sizeof(View), hipMemcpyHostToDevice));
-    d.view_hot = v.hot; d.view_fact_and = v.fact_and;
+    d.view_hot = v.hot; d.view_fact_and = v.fact_and; d.view_col_and = v.col_and;
     d.wl.nwaves = (uint32_t)((nres + WAVE - 1) / WAVE);
     const size_t nwv = d.wl.nwaves;
     // rule slices: consecutive rules while their walk buffers fit the budget (and every slice-local index fits 32 bits)
@@ -2136,10 +2144,10 @@ void eval_gpu(const Ruleset& rs, const Batch& b, int device, int iters, Results*
     db->out = dd;
   }
   DeviceResults& d = *db->out;
-  if (d.view_hot != v.hot || d.view_fact_and != v.fact_and) {
+  if (d.view_hot != v.hot || d.view_fact_and != v.fact_and || d.view_col_and != v.col_and) {
     // (no evaluation of this batch is in flight here: each one ends synchronised with its streams)
     HIP_OK(hipMemcpy(d.view, &v, sizeof(View), hipMemcpyHostToDevice));
-    d.view_hot = v.hot; d.view_fact_and = v.fact_and;
+    d.view_hot = v.hot; d.view_fact_and = v.fact_and; d.view_col_and = v.col_and;
   }
   hipStream_t stream = d.stream;
   const bool use_jit = jit_mode == JIT_ON || (jit_mode == JIT_AUTO && nres >= JIT_AUTO_MIN_RESOURCES);

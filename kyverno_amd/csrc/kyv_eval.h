@@ -109,6 +109,10 @@ struct View {
   // KYV_FACT_MAPS switch sets it to 0, "nothing known"
   const WaveFacts* facts;
   uint32_t fact_and;
+  // column facts (kyv_layout.h ColFacts), one row per match wave, or nullptr; a kernel uses (empty & col_and): the
+  // KYV_FACT_COLS switch sets it to 0, "nothing known"
+  const ColFacts* col_facts;
+  uint64_t col_and;
   const FloatAux* faux;
   const uint32_t* str_off;
   const uint32_t* str_len;

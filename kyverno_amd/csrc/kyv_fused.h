@@ -86,7 +86,8 @@ __device__ __forceinline__ void walk_shapes(const View& v, const ShapeOut& so, S
       cls = h.kclass;
     }
     (void)hnn;
-    f.run(v, so, r, active, hflags, hroot, cls, wave_maps(v, w));
+    if constexpr (takes_col_facts<Shapes>::value) f.run(v, so, r, active, hflags, hroot, cls, wave_maps(v, w), wave_cols(v, w).empty);
+    else f.run(v, so, r, active, hflags, hroot, cls, wave_maps(v, w));
   }
 }
 

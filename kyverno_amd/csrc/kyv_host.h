@@ -151,6 +151,9 @@ struct Ruleset {
   // per-wave facts (compiler.cpp assign_wave_facts): all-maps bit j <-> row space fact_spaces[j]; the flattener
   // (Batch::facts) and the generated kernels (jit.cpp) number bits by it
   std::vector<uint32_t> fact_spaces;
+  // column facts (kyv_layout.h ColFacts, compiler.cpp assign_col_facts): empty bit j <-> the "[*]" position held by trie
+  // node fact_lists[j] (trie order, at most COLFACT_BITS)
+  std::vector<uint32_t> fact_lists;
   // meta-key classes (compiler.cpp assign_meta_classes, kyv_layout.h MetaClass): meta_class_of[site] = the class of
   // metadata site `site` (index into metas) or -1: the site keeps expand_meta. Host, device (the fill kernel reads the
   // uploaded classes) and generated code number classes by this list.
@@ -158,6 +161,7 @@ struct Ruleset {
   std::vector<int8_t> meta_class_of;
   bool jit_meta_keys = false;       // the generated source reads the meta-key plane (set with jit_tried)
   int jit_jc_chains = 0;           // the condition rules' field chains read their last step alone (set with jit_tried)
+  int jit_col_facts = 0;           // the generated source reads the column facts (jit_col_facts_mode; set with jit_tried)
   // runtime-compiled walk kernel (jit.cpp): generated once per ruleset, compiled on first use
   bool jit_tried = false;
   std::vector<uint8_t> jit_rules;   // rule k is walked by the compiled kernel
@@ -215,6 +219,7 @@ struct Batch {
   std::vector<uint32_t> col_off, rs_rows;
   // per-wave facts (kyv_layout.h WaveFacts), one row per match wave of 64 resources, filled by resolve_path_columns
   std::vector<WaveFacts> facts;
+  std::vector<ColFacts> col_facts;  // (kyv_layout.h ColFacts) likewise, one row per match wave
   std::vector<void*> dev;
   ~Batch();
 };
@@ -273,6 +278,7 @@ Batch* build_batch(const Ruleset* rs, const char* json, size_t len, const char* 
 void derive_strings(Batch& b, size_t from, int threads);
 void build_path_trie(Ruleset& rs);
 void assign_wave_facts(Ruleset& rs);
+void assign_col_facts(Ruleset& rs);
 void assign_meta_classes(Ruleset& rs);
 // KYV_META_KEYS=0: the generated source resolves wildcard metadata keys in the walk (expand_meta) as before round 10,
 // and no meta-key plane is filled; read when the source is generated
@@ -285,6 +291,12 @@ size_t meta_key_plane_bytes(const Batch& b);  // bytes of the batch's plane on o
 // KYV_FACT_MAPS=0: the batch reports "nothing known" (every all-maps bit clear) to the kernels and to
 // kyv_batch_wave_facts; read per evaluation, no recompile
 uint32_t wave_maps_mask();  // AND-ed with a row's all-maps word
+// KYV_FACT_COLS=0: likewise for the column facts (every ColFacts row reads as zero)
+uint64_t col_facts_mask();
+// KYV_JIT_COLFACTS: what the generated source does with the column facts -- bit 0: loads of the entry and length
+// columns of a "[*]" position take no row where the wave's empty bit is set. Default 1; 0 whenever KYV_JC_PRELOAD=0 or
+// KYV_META_KEYS=0 is set (those stand for the sources of earlier rounds); read when the source is generated
+int jit_col_facts_mode();
 void assign_glob_masks(Ruleset& rs);
 void assign_cond_sets(Ruleset& rs);
 // KYV_JC_PRELOAD: the compiled condition rules read the last step of a static field chain alone (jit.cpp CondGen
@@ -293,9 +305,10 @@ void assign_cond_sets(Ruleset& rs);
 int jit_jc_chains_mode();
 // meta_keys: 1 / 0 = the source reads / does not read the meta-key plane, -1 = as KYV_META_KEYS says now;
 // jc_chains: 1 / 0 = the condition rules' field chains read / do not read their last step alone, -1 = as
-// KYV_JC_PRELOAD says now
+// KYV_JC_PRELOAD says now; col_facts: the KYV_JIT_COLFACTS bits, -1 = as the environment says now
 std::string jit_source(const Ruleset& rs, std::vector<uint8_t>* jit_rules, std::vector<uint8_t>* jit_cond = nullptr,
-                       std::vector<uint16_t>* jit_shape = nullptr, int meta_keys = -1, int jc_chains = -1);
+                       std::vector<uint16_t>* jit_shape = nullptr, int meta_keys = -1, int jc_chains = -1,
+                       int col_facts = -1);
 // pattern rules the shape tables can decide (kyv_jit_shapes): a covered RK_PATTERN rule without metadata expansion,
 // preconditions or a fused walk (its match program runs in the match phase)
 bool jit_shape_eligible(const Ruleset& rs, uint32_t k);

@@ -28,6 +28,11 @@ __device__ __forceinline__ uint64_t jc_col(const View& v, uint32_t col, uint32_t
   const uint32_t off = sld32(v.col_off + col);
   return gcol(v.colv, off, row);
 }
+// the empty-list facts of the wave that resource r belongs to (kyv_layout.h ColFacts::empty; r = 64 w + lane, so r >> 6
+// is wave-uniform): one scalar load, once per generated rule function (jit.cpp CondGen: jr<k> hands it down)
+__device__ __forceinline__ uint64_t jc_empty(const View& v, uint32_t r) {
+  return wave_cols(v, __builtin_amdgcn_readfirstlane(r >> 6)).empty;
+}
 // the meta-key plane row of (class, resource row) (kyv_layout.h MetaKeyRow): one 16-byte load per lane, a wave's 64
 // rows whole lines; issued with the root scope's column loads (jit.cpp Gen::preload)
 __device__ __forceinline__ kyv_u32x4 jc_meta(const View& v, uint32_t cls, uint32_t row) {

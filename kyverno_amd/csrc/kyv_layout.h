@@ -153,6 +153,19 @@ struct WaveFacts {
 };
 static_assert(sizeof(WaveFacts) == 4, "wave facts row size");
 
+// Column facts (round 14): a second plane beside WaveFacts, one 8-byte row per match wave, filled by the same pass of
+// the flattener and read with one scalar load per wave. Bit numbering: compiler.cpp assign_col_facts.
+//   empty bit j:   no resource of the wave has any entry in the entry column of "[*]" position j of the path trie
+//                  (Ruleset::fact_lists[j], trie order; at a nested position: no parent-space row the wave's resources
+//                  own has one). The value there is absent everywhere: a list that is present and empty, a null and a
+//                  value of another type all have an entry and clear the bit. Positions past COLFACT_BITS have no bit.
+// "Nothing known" is all zero: every load is issued as before round 14.
+constexpr uint32_t COLFACT_BITS = 64;
+struct ColFacts {
+  uint64_t empty;
+};
+static_assert(sizeof(ColFacts) == 8, "column facts row size");
+
 // ---------------------------------------------------------------- match programs
 enum MatchMode : uint8_t { MM_NONE = 0, MM_PLAIN = 1, MM_ANY = 2, MM_ALL = 3,
                            MM_EXC_ALL = 4 };  // a PolicyException match with neither any nor all: matches everything

@@ -95,6 +95,20 @@ __device__ __forceinline__ HotHdr ghot(const View& v, uint32_t r) {
 __device__ __forceinline__ uint32_t wave_maps(const View& v, uint32_t w) {
   return v.facts ? (sld32(&v.facts[w].maps) & v.fact_and) : 0u;
 }
+// Column facts of match wave w (kyv_layout.h ColFacts; w wave-uniform: one 8-byte scalar load), the run-time switch
+// applied; without the plane nothing is known
+__device__ __forceinline__ ColFacts wave_cols(const View& v, uint32_t w) {
+  ColFacts f{0ull};
+  if (v.col_facts) {
+    f = sld(v.col_facts + w);
+    f.empty &= v.col_and;
+  }
+  return f;
+}
+// A walker or shape table of a source generated with the column facts (jit.cpp KYV_JIT_COLFACTS) declares
+// `static constexpr bool kColFacts = true` and takes the wave's row; the sources of earlier rounds do neither
+template <class W, class = void> struct takes_col_facts { static constexpr bool value = false; };
+template <class W> struct takes_col_facts<W, decltype((void)W::kColFacts)> { static constexpr bool value = W::kColFacts; };
 // one header word alone (a compiled map function's metadata-shape flags: jit.cpp)
 __device__ __forceinline__ uint32_t ghot_flags(const View& v, const ResHeader* hp) {
   KYV_ACCT_ADD(0, 4);
@@ -716,6 +730,8 @@ struct JW {
   uint32_t am;           // the wave's all-maps facts (WaveFacts::maps; wave-uniform)
   const Val* dyn = nullptr;  // the rule's resolved `{{ request.object... }}` pattern variables (its root function's
                              // dv[]; L_DYN leaves index it with constants), nullptr for a rule without any
+  uint64_t ce = 0ull;        // the wave's empty-list facts (ColFacts::empty; wave-uniform), set by a root function of a
+                             // source generated with them
 };
 // one simple comparison with the atom's operator, flags and glob class as template constants (the generated
 // leaf code instantiates exactly the branches watom_simple would take for that atom)
@@ -945,6 +961,7 @@ __device__ __forceinline__ void walk_chunks(const View& v, DevOut o, WorkLists w
     }
     wk.rootmap = (it.x & ITEM_ROOT_MAP) != 0;
     wk.am = wave_maps(v, w);  // a chunk's resources are those of match wave w
+    if constexpr (takes_col_facts<Walker>::value) wk.ce = wave_cols(v, w).empty;
     const uint32_t alts = rd.kind == RK_PATTERN ? 1u : min(rd.nalts, (uint32_t)MAX_ALTS);
     WaveSink sink{o.stage + sld32(o.rbase + (k - o.rule_lo)) + (size_t)w * WAVE * alts, 0u, rd.uses_meta != 0};
     uint8_t st = pair_walk(v, rd, active, r, k, v.nodes + it.y, wk, sink);

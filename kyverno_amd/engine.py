@@ -143,6 +143,19 @@ class Batch:
         return dict(json.loads(bits.value.decode()), facts=facts, hot=hot, order=order, shape_keys=keys,
                     shape_paths=shape["paths"], shape_bits=shape["bits"], shape_ordered=shape["ordered"])
 
+    def col_facts(self):
+        """The batch's column facts (kyv_batch_col_facts): `rows` uint64 [waves] -- the `empty` word of each match
+        wave (batch order, see `wave_facts` `order`) -- and the bits' meaning: `lists`, the path of the list position
+        of each bit"""
+        L = K.lib()
+        o = K.ColFactsOut()
+        K.check(L.kyv_batch_col_facts(self.h, ctypes.byref(o)))
+        rows = np.zeros((self.n + 63) // 64, dtype=np.uint64)
+        bits = ctypes.create_string_buffer(o.bits_len + 1)
+        o = K.ColFactsOut(rows.ctypes.data, rows.size, ctypes.addressof(bits), o.bits_len + 1, 0)
+        K.check(L.kyv_batch_col_facts(self.h, ctypes.byref(o)))
+        return dict(json.loads(bits.value.decode()), rows=rows)
+
     def meta_keys(self, device=None):
         """The batch's meta-key plane (kyv_batch_meta_keys): what each wildcard metadata site class of the ruleset
         resolves to for every resource -- `rows` uint32 [classes, n, 4] (resources in batch order, see `wave_facts`
